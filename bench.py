@@ -14,6 +14,10 @@ nan_to_num + clip, the RCCL all-reduce of the flat policy gradient when N > 1, a
     python bench.py --gpus N ...        # no RANK in the environment: bench.py starts that torch.distributed.run itself
 
 Weak scaling: every rank owns 4 envs; `value` is the whole-job aggregate.  Rank 0 prints ONE JSON line.
+
+A plain run of the headline line does only what `value` needs: set up, warm up, time --steps updates, print the line.  `--full` adds
+the forward-only rate, the same update in the reference's operation order (`reference_order`), the many-env saturation probe and the
+CPU baselines.  `--dump-outputs DIR` writes what the last timed update computed as DIR/<name>.npy (float32).
 """
 from __future__ import annotations
 
@@ -154,6 +158,21 @@ def dist_info(world, allreduce_params=0):
     one collective per update (the policy-gradient mean, apg.py:235); 0 for simulator-only workloads (replicas, no collective)."""
     return {"n_ranks_seen": dist.get_world_size() if dist.is_initialized() else 1,
             "allreduce_bytes_per_update": allreduce_params * 4 if world > 1 else 0}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy in float32 (the tensors come off the device here, after the timed region), so that
+    two builds run with the same arguments -- hence the same seeds and inputs -- can be compared output for output."""
+    host = {k: torch.as_tensor(v).detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
 
 
 def lg_label(dom, sim, B):
@@ -1067,7 +1086,19 @@ def main():
     ap.add_argument("--kernel-mode", type=int, default=0,
                     help="cloth kernel family (include/unidom_hip.h): 0 default (v2-order forward, bit-exact vs the restatement of that order), "
                          "1 reference-order forward + literal adjoint, 2 fast-math, 3 reference-order forward + restructured adjoint")
+    ap.add_argument("--full", action="store_true",
+                    help="fold_cloth1 / fold_cloth1_para: also run what the headline figure does not need -- the forward-only rate, the same update "
+                         "in the reference's operation order, the many-env saturation probe and the CPU baselines (each still subject to its "
+                         "--no-* switch).  Off: set up, warm up, time --steps updates, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="fold_cloth1 / fold_cloth1_para: after the timed steps, write what the last timed update returned (loss, per-step "
+                         "reward, gradient norm) and left behind (the clipped flat policy gradient, the updated flat policy parameters) "
+                         "as DIR/<name>.npy, float32")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (ms_per_step is the time of one timed step)")
+    if args.dump_outputs and args.workload not in ("fold_cloth1", "fold_cloth1_para"):
+        ap.error("--dump-outputs is implemented for the fold_cloth1 / fold_cloth1_para line only")
     if args.gpus > 1 and "RANK" not in os.environ:
         self_launch(sys.argv[1:])              # never returns; nothing above has touched a GPU
 
@@ -1129,13 +1160,17 @@ def main():
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        learner.minimize(state)
+        last = learner.minimize(state)
     sync()
     dt = time.perf_counter() - t0
     prof = env.simulator.profile
     env.simulator.profile = None
     ranks = rank_report(world, device, dt, {k: float(np.mean([a.elapsed_time(b) for a, b in v])) for k, v in prof.items() if v}, learner.sync)
     learner.sync.profile = None
+    if args.dump_outputs and rank == 0:   # before anything below touches the learner again
+        dump_outputs(args.dump_outputs, {"loss": last["loss"], "reward": last["reward"], "grad_norm": last["grad_norm"],
+                                         "policy_grad": learner.flat_grad,
+                                         "policy_params": torch.cat([p.detach().reshape(-1) for p in learner.params])})
 
     graph_line = None
     if want_graph:
@@ -1154,18 +1189,20 @@ def main():
             graph_line = {"error": f"{type(e).__name__}: {e}"}
 
     # forward-only rate (BASELINE config 2), untimed region of the main metric
-    with torch.no_grad():
-        sync()
-        tf0 = time.perf_counter()
-        for _ in range(args.steps):
-            learner.evaluate(state, EP_LEN)
-        sync()
-        dt_fwd = time.perf_counter() - tf0
+    dt_fwd = float("nan")
+    if args.full:
+        with torch.no_grad():
+            sync()
+            tf0 = time.perf_counter()
+            for _ in range(args.steps):
+                learner.evaluate(state, EP_LEN)
+            sync()
+            dt_fwd = time.perf_counter() - tf0
 
     # the same update in the reference's LITERAL operation order (ud_cloth_conf.mode 3: cloth_simulator.py:257-337 as written, forward
     # bit-exact vs the restatement of that order + the restructured adjoint), timed exactly like the headline -- reported beside it
     ref_line, dt_ref, k_ms_ref = None, float("nan"), {}
-    if args.kernel_mode == 0:
+    if args.full and args.kernel_mode == 0:
         conf3 = DefaultConf()
         conf3.kernel_mode = 3
         if para:
@@ -1218,7 +1255,6 @@ def main():
                        "parallelism": f"env-sharded dp{world}, 1 RCCL all-reduce of {learner.n_params} f32 per update"},
             "n_ranks_seen": dist.get_world_size() if dist.is_initialized() else 1,
             "allreduce_bytes_per_update": learner.n_params * 4 if world > 1 else 0,
-            "fwd_only_substeps_per_sec": units / dt_fwd,
             "roofline": {"bound": "hbm", "kernel": kname, "achieved": achieved,
                          "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
                          "kernel_ms": k_ms, "algorithmic_bytes_per_launch": per_launch,
@@ -1226,7 +1262,9 @@ def main():
                                  "about this kernel -- see `issue` (instruction issue on the busy CUs) and `saturation`",
                          "issue": issue_roof(kname, k_ms[dom], 8 * NUM_ENVS_PER_GPU, NUM_ENVS_PER_GPU, MACRO * SUBSTEPS)},
         }
-        if args.kernel_mode == 0:
+        if args.full:
+            out["fwd_only_substeps_per_sec"] = units / dt_fwd
+        if args.full and args.kernel_mode == 0:
             out["reference_order"] = {
                 "value": units / dt_ref, "unit": "substeps/s", "ms_per_step": dt_ref / args.steps * 1e3, "kernel_ms": k_ms_ref, "kernel_mode": 3,
                 "kernels": {"fwd": "cloth_rollout_fwd_ref_kernel", "bwd": "cloth_rollout_bwd_fast_kernel"},
@@ -1244,9 +1282,9 @@ def main():
         out.update(ranks)
         if graph_line is not None:
             out["hip_graph"] = graph_line
-        if not args.no_saturation:
+        if args.full and not args.no_saturation:
             out["saturation"] = saturation_probe(env, device)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(sample_envs=min(NUM_ENVS_PER_GPU, max(4, host_cores())),
                                                gpu_order=1 if args.kernel_mode in (1, 3) else 2)
         print(json.dumps(out), flush=True)

@@ -6,14 +6,48 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_cli_accepts_the_driver_arguments():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup", "--workload"):
+    for flag in ("--gpus", "--steps", "--warmup", "--workload", "--full", "--dump-outputs"):
         assert flag in out.stdout
+
+
+def test_dump_outputs_writes_float32_npy_within_the_limit(tmp_path):
+    """--dump-outputs: every array lands as DIR/<name>.npy in float32 with its shape and values; more than 64 MB in all is refused."""
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    arrays = {"loss": torch.tensor(-0.5, dtype=torch.float32), "reward": torch.arange(12, dtype=torch.float64).reshape(3, 4),
+              "policy_params": torch.linspace(-1, 1, 1000)}
+    bench.dump_outputs(str(tmp_path / "out"), arrays)
+    for k, v in arrays.items():
+        a = np.load(tmp_path / "out" / f"{k}.npy")
+        assert a.dtype == np.float32 and a.shape == tuple(v.shape)
+        assert np.array_equal(a, v.float().numpy())
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": torch.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1)})
+    assert not (tmp_path / "big").exists()
+
+
+def test_bench_refuses_zero_timed_steps(tmp_path):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0", "--dump-outputs", str(tmp_path / "out")],
+                         capture_output=True, text=True, timeout=120)
+    assert out.returncode == 2 and "--steps" in out.stderr
+    assert not (tmp_path / "out").exists()
+
+
+def test_dump_outputs_refuses_a_workload_it_does_not_cover(tmp_path):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "selftest", "--dump-outputs", str(tmp_path / "out")],
+                         capture_output=True, text=True, timeout=120)
+    assert out.returncode == 2 and "--dump-outputs" in out.stderr
+    assert not (tmp_path / "out").exists()
 
 
 def test_committed_headline_line_has_the_contract_keys():

@@ -192,6 +192,46 @@ def test_fused_chamfer_matches_op_by_op(P, Q, B):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("P,Q,B", [(512, 512, 4), (17, 700, 3)])
+def test_fused_chamfer_is_bit_reproducible(P, Q, B):
+    """No arrival-ordered float sums in the chamfer: the same input gives the same bits, forward and backward, call after call --
+    also where many goal points share one argmin (P=17, Q=700: ~41 per particle, what an atomic scatter would reorder)."""
+    from unidom_amd.envs.basic import _fused
+    g = torch.Generator(device="cuda").manual_seed(P * Q)
+    x0 = torch.rand((B, P, 3), device="cuda", generator=g)
+    y = torch.rand((Q, 3), device="cuda", generator=g)
+    w = torch.rand((B,), device="cuda", generator=g) + 0.5
+    runs = []
+    for _ in range(4):
+        x = x0.clone().requires_grad_(True)
+        out = _fused.chamfer(x, y)
+        (gx,) = torch.autograd.grad((out * w).sum(), x)
+        runs.append((out.detach(), gx))
+    for out, gx in runs[1:]:
+        assert torch.equal(out, runs[0][0]) and torch.equal(gx, runs[0][1])
+
+
+@pytest.mark.gpu
+def test_fold_cloth1_update_is_bit_reproducible():
+    """bench.py's headline update (fold_cloth1, 4 envs, ep_len 3, the same seeds): two learners built alike take the same two
+    updates bit for bit -- rewards, loss, gradient norm, clipped gradient and parameters, what `bench.py --dump-outputs` writes."""
+    from unidom_amd.algorithms.apg.core import APG
+    from unidom_amd.envs.registration import env_functions
+    from unidom_amd.utils import prng
+    res = []
+    for _ in range(2):
+        env = env_functions["fold_cloth1"](batch_size=4, seed=0, aux_reward=True, device="cuda:0")
+        learner = APG(env, 3, learning_rate=1e-4, max_gradient_norm=0.3, seed=0)
+        _, st = env.reset(prng.split(prng.PRNGKey(0), 1)[0])
+        for _ in range(2):
+            m = learner.minimize(st)
+        res.append([m["reward"], m["loss"], m["grad_norm"], learner.flat_grad.clone(),
+                    torch.cat([p.detach().reshape(-1) for p in learner.params])])
+    for a, b in zip(*res):
+        assert torch.equal(a, b)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("bad", ["nan", "inf", "all_nan", "all_inf"])
 def test_fused_chamfer_and_contact_with_non_finite_particles(bad):
     """One NaN / inf particle (or a whole non-finite cloud) must not turn into an out-of-range argmin: the index the

@@ -10,7 +10,7 @@ if want 1; then
 timeout -k 10 1100 python -m pytest tests -q -m gpu 2>&1 | tail -8 > $O/${TAG}_gpu_tests.log; tail -2 $O/${TAG}_gpu_tests.log
 timeout -k 10 300 python tools/det_cost.py > $O/${TAG}_det_cost.txt 2>$O/det_cost.err; cat $O/${TAG}_det_cost.txt
 fi
-run() { name=$1; shift; timeout -k 10 300 python bench.py "$@" 2>$O/$name.err | tail -n 1 > $O/${TAG}_bench_line_$name.json
+run() { name=$1; shift; timeout -k 10 300 python bench.py --full "$@" 2>$O/$name.err | tail -n 1 > $O/${TAG}_bench_line_$name.json
   python - <<PY
 import json
 d = json.load(open("$O/${TAG}_bench_line_$name.json"))
@@ -21,7 +21,7 @@ if ro: print("   reference_order", round(ro["value"]), ro["kernel_ms"], "cpu ord
 print("$name", round(d["value"]), "%.2f ms" % d["ms_per_step"], "frac %.4f" % d["roofline"]["frac"], d["roofline"].get("kernel_ms"), "traffic", d["roofline"].get("traffic"), "issue", i, "cpu", (d.get("cpu_baseline") or {}).get("value"))
 PY
   if [ -n "$KS" ]; then
-    rm -rf $O/ks_$name; timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/ks_$name -o p -f csv -- python3 bench.py "$@" --no-cpu-baseline --no-saturation > $O/ks_$name.log 2>&1 \
+    rm -rf $O/ks_$name; timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/ks_$name -o p -f csv -- python3 bench.py --full "$@" --no-cpu-baseline --no-saturation > $O/ks_$name.log 2>&1 \
       && cp $O/ks_$name/p_kernel_stats.csv $O/${TAG}_kernel_stats_$name.csv && rm -rf $O/ks_$name
   fi
 }

@@ -1,7 +1,9 @@
 // Cloth-env arithmetic either side of the rollout, fused: the reference jit-compiles step_diff, so XLA turns the
 // chamfer reward, the contact distance and the 6-vector -> 40 x 8 macro-action expansion into a handful of fused
 // kernels; done op by op on the device they are ~180 tiny launches (and a dense [B,P,Q] autograd graph) per
-// step_diff.  Here each piece is one forward and one backward kernel, one workgroup per environment.
+// step_diff.  Here each piece is one forward and one backward kernel, one workgroup per environment -- the chamfer forward is two:
+// the argmin scan, then a fixed-order sum of the two means.  No float sum in this half depends on arrival order, so the same
+// input gives the same bits on every run.
 // The MPM envs' counterpart (focus shift before the step; un-shift, nan_to_num, reward and observation after it) is the
 // second half of this file.
 //   chamfer        core/utils/util.py:138-153     d(p,q) = sqrt(mean_xyz((x_p - y_q)^2)); mean_p min_q + mean_q min_p
@@ -45,12 +47,13 @@ __device__ __forceinline__ float block_sum(float v, float* scratch) {
 // ---- chamfer -------------------------------------------------------------------------------------
 // grid (B, tiles, 2): z = 0 scans, for 64 particles per workgroup, all goal points; z = 1 the other way round.
 // Four lanes share a row (each takes every fourth column), the quad then reduces (value, first index) with DPP.
-// The two means are accumulated into out[b] (zeroed by the caller) with one atomic per workgroup.
+// The kernel stores the argmins only; chamfer_sum_kernel turns them into the two means in a fixed order (no float atomics:
+// the same input gives the same bits on every run).
 constexpr int CH_ROWS = GLUE_T / 4;
 
 __global__ void __launch_bounds__(GLUE_T) chamfer_fwd_kernel(int P, int Q, const float* __restrict__ x, const float* __restrict__ y,
-                                                             float* __restrict__ out, int* __restrict__ ixy, int* __restrict__ iyx) {
-  extern __shared__ float lds[];   // cols[3][nc] | scratch[8]
+                                                             int* __restrict__ ixy, int* __restrict__ iyx) {
+  extern __shared__ float lds[];   // cols[3][nc]
   const int b = blockIdx.x, tid = threadIdx.x, dir = blockIdx.z;
   const float* xb = x + (size_t)b * P * 3;
   const float* rows = dir == 0 ? xb : y;
@@ -59,7 +62,6 @@ __global__ void __launch_bounds__(GLUE_T) chamfer_fwd_kernel(int P, int Q, const
   const int r0 = blockIdx.y * CH_ROWS;
   if (r0 >= nr) return;   // uniform: the grid is sized for the larger cloud
   float* cs = lds;
-  float* scratch = lds + 3 * nc;
   for (int i = tid; i < nc; i += GLUE_T) { cs[i] = cols[i * 3]; cs[nc + i] = cols[i * 3 + 1]; cs[2 * nc + i] = cols[i * 3 + 2]; }
   __syncthreads();
   const int r = r0 + (tid >> 2), c0 = tid & 3;
@@ -77,20 +79,37 @@ __global__ void __launch_bounds__(GLUE_T) chamfer_fwd_kernel(int P, int Q, const
     const float ov = __shfl_xor(best, off); const int oi = __shfl_xor(bi, off);
     if (min_takes(ov, oi, best, bi)) { best = ov; bi = oi; }
   }
-  float s = 0.f;
-  if (live && c0 == 0) {
-    (dir == 0 ? ixy + (size_t)b * P : iyx + (size_t)b * Q)[r] = bi;
-    s = sqrtf(best);   // min of sqrt == sqrt of min (sqrtf is monotone)
+  if (live && c0 == 0) (dir == 0 ? ixy + (size_t)b * P : iyx + (size_t)b * Q)[r] = bi;
+}
+
+// grid (B): out[b] = mean_p sqrt(d(p, ixy[p])) + mean_q sqrt(d(iyx[q], q)).  d is recomputed from the stored argmin with the
+// forward's own arithmetic, so it is the minimum the forward found, bit for bit (min of sqrt == sqrt of min: sqrtf is monotone).
+// Fixed order: every thread sums its rows tid, tid + GLUE_T, ... in turn, then one block_sum per direction.
+__global__ void __launch_bounds__(GLUE_T) chamfer_sum_kernel(int P, int Q, const float* __restrict__ x, const float* __restrict__ y,
+                                                             const int* __restrict__ ixy, const int* __restrict__ iyx, float* __restrict__ out) {
+  __shared__ float scratch[GLUE_T / 64];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const float* xb = x + (size_t)b * P * 3;
+  const int* jp = ixy + (size_t)b * P;
+  const int* jq = iyx + (size_t)b * Q;
+  float sp = 0.f, sq = 0.f;
+  const int big = P > Q ? P : Q;
+  for (int r = tid; r < big; r += GLUE_T) {
+    if (r < P) { const int c = jp[r]; sp += sqrtf(mean_sq3(xb[r * 3], xb[r * 3 + 1], xb[r * 3 + 2], y[c * 3], y[c * 3 + 1], y[c * 3 + 2])); }
+    if (r < Q) { const int c = jq[r]; sq += sqrtf(mean_sq3(xb[c * 3], xb[c * 3 + 1], xb[c * 3 + 2], y[r * 3], y[r * 3 + 1], y[r * 3 + 2])); }
   }
-  const float t = block_sum(s, scratch);
-  if (tid == 0) atomicAdd(&out[b], t / (float)nr);
+  const float tp = block_sum(sp, scratch);
+  const float tq = block_sum(sq, scratch);
+  if (tid == 0) out[b] = tp / (float)P + tq / (float)Q;
 }
 
 __global__ void __launch_bounds__(GLUE_T) chamfer_bwd_kernel(int P, int Q, const float* __restrict__ x, const float* __restrict__ y,
                                                              const int* __restrict__ ixy, const int* __restrict__ iyx,
                                                              const float* __restrict__ g_out, float* __restrict__ g_x) {
-  extern __shared__ float lds[];   // gx[P][3]
-  float* gx = lds;
+  extern __shared__ float lds[];   // cp[GLUE_T] | cc[GLUE_T][3] | gx[P][3]  (cp first: read as int4)
+  int* cp = (int*)lds;
+  float* cc = lds + GLUE_T;
+  float* gx = cc + 3 * GLUE_T;
   const int b = blockIdx.x, tid = threadIdx.x;
   const float* xb = x + (size_t)b * P * 3;
   const float g = g_out[b];
@@ -103,14 +122,46 @@ __global__ void __launch_bounds__(GLUE_T) chamfer_bwd_kernel(int P, int Q, const
     gx[p * 3] = c * dx; gx[p * 3 + 1] = c * dy; gx[p * 3 + 2] = c * dz;
   }
   __syncthreads();
-  for (int q = tid; q < Q; q += GLUE_T) {
-    const int p = iyx[(size_t)b * Q + q];
-    const float dx = xb[p * 3] - y[q * 3], dy = xb[p * 3 + 1] - y[q * 3 + 1], dz = xb[p * 3 + 2] - y[q * 3 + 2];
-    const float d = sqrtf((dx * dx + dy * dy + dz * dz) / 3.0f);
-    const float c = gq / (3.0f * d);
-    atomicAdd(&gx[p * 3], c * dx); atomicAdd(&gx[p * 3 + 1], c * dy); atomicAdd(&gx[p * 3 + 2], c * dz);
+  // the goal side scatters onto argmins that several q may share.  Per chunk of GLUE_T goal points each wave takes its 64: the
+  // first lane of the wave that names a particle sums the wave's contributions to it in q order, then the four waves add their
+  // sums to gx in wave order -- a fixed order, so the same bits on every run
+  const int lane = tid & 63, wv = tid >> 6;
+  for (int q0 = 0; q0 < Q; q0 += GLUE_T) {
+    const int q = q0 + tid;
+    int p = -1;
+    if (q < Q) {
+      p = iyx[(size_t)b * Q + q];
+      const float dx = xb[p * 3] - y[q * 3], dy = xb[p * 3 + 1] - y[q * 3 + 1], dz = xb[p * 3 + 2] - y[q * 3 + 2];
+      const float d = sqrtf((dx * dx + dy * dy + dz * dz) / 3.0f);
+      const float c = gq / (3.0f * d);
+      cc[tid * 3] = c * dx; cc[tid * 3 + 1] = c * dy; cc[tid * 3 + 2] = c * dz;
+    }
+    cp[tid] = p;
+    __syncthreads();
+    bool first = p >= 0;
+    float sx = 0.f, sy = 0.f, sz = 0.f;
+    if (first) {   // one pass over the wave's 64 slots (every lane reads the same words: LDS broadcast); unused slots hold -1
+      sx = cc[tid * 3]; sy = cc[tid * 3 + 1]; sz = cc[tid * 3 + 2];
+      const int4* cp4 = (const int4*)(cp + wv * 64);
+#pragma unroll 4
+      for (int j4 = 0; j4 < 16; ++j4) {
+        const int4 v = cp4[j4];
+        const int e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const int j = j4 * 4 + k;
+          if (e[k] == p && j != lane) {
+            if (j < lane) first = false;
+            else { const float* o = cc + (wv * 64 + j) * 3; sx += o[0]; sy += o[1]; sz += o[2]; }
+          }
+        }
+      }
+    }
+    for (int w = 0; w < GLUE_T / 64; ++w) {
+      if (wv == w && first) { gx[p * 3] += sx; gx[p * 3 + 1] += sy; gx[p * 3 + 2] += sz; }
+      __syncthreads();
+    }
   }
-  __syncthreads();
   float* o = g_x + (size_t)b * P * 3;
   for (int i = tid; i < P * 3; i += GLUE_T) o[i] = gx[i];
 }
@@ -376,10 +427,11 @@ int ud_chamfer_fwd(int B, int P, int Q, const float* x, const float* y, float* o
   if (B <= 0 || P <= 0 || Q <= 0 || !x || !y || !out || !idx_xy || !idx_yx) { set_error("ud_chamfer_fwd: bad argument"); return UD_ERR_INVALID; }
   if (P > GLUE_MAXPTS || Q > GLUE_MAXPTS) { set_error("ud_chamfer_fwd: P=%d / Q=%d above the %d points staged in LDS", P, Q, GLUE_MAXPTS); return UD_ERR_UNSUPPORTED; }
   const int big = P > Q ? P : Q;
-  const size_t shmem = (size_t)(3 * big + 8) * sizeof(float);
-  UD_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)B * sizeof(float), (hipStream_t)stream));
+  const size_t shmem = (size_t)3 * big * sizeof(float);
   hipLaunchKernelGGL(chamfer_fwd_kernel, dim3(B, (big + CH_ROWS - 1) / CH_ROWS, 2), dim3(GLUE_T), shmem, (hipStream_t)stream, P, Q, x, y,
-                     out, idx_xy, idx_yx);
+                     idx_xy, idx_yx);
+  UD_HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(chamfer_sum_kernel, dim3(B), dim3(GLUE_T), 0, (hipStream_t)stream, P, Q, x, y, idx_xy, idx_yx, out);
   UD_HIP_CHECK(hipGetLastError());
   return UD_OK;
 }
@@ -388,7 +440,7 @@ int ud_chamfer_bwd(int B, int P, int Q, const float* x, const float* y, const in
                    float* g_x, void* stream) {
   if (B <= 0 || P <= 0 || Q <= 0 || !x || !y || !idx_xy || !idx_yx || !g_out || !g_x) { set_error("ud_chamfer_bwd: bad argument"); return UD_ERR_INVALID; }
   if (P > GLUE_MAXPTS) { set_error("ud_chamfer_bwd: P=%d above %d", P, GLUE_MAXPTS); return UD_ERR_UNSUPPORTED; }
-  const size_t shmem = (size_t)3 * P * sizeof(float);
+  const size_t shmem = (size_t)(3 * P + 4 * GLUE_T) * sizeof(float);
   hipLaunchKernelGGL(chamfer_bwd_kernel, dim3(B), dim3(GLUE_T), shmem, (hipStream_t)stream, P, Q, x, y, idx_xy, idx_yx, g_out, g_x);
   UD_HIP_CHECK(hipGetLastError());
   return UD_OK;
