@@ -126,6 +126,75 @@ static void rollout_bwd(const OcCloth* h, int B, int TT, const T* x0, const T* v
   }
 }
 
+// The f32 trajectory's adjoint in f64 ("A64"): each env's forward and per-substep checkpoint run in f32 in the handle's
+// order (bit-identical to the HIP forward of the matching mode); every checkpointed state is cast to f64 and swept back by
+// cloth_substep_bwd<double> with the f64 tables and parameters.  The sweep takes its grasp sets from the f32 forward's record
+// and counts, in *flips, the particles where its own f64 test `dist <= radius` decides otherwise.  Cotangents and outputs
+// are f64; the inputs are the f32 values the forward ran on.
+static void rollout_bwd_mixed(const OcCloth* h, int B, int TT, const float* x0, const float* v0, const float* prim0,
+                              const float* k, const float* mu, const float* actions, const double* gx, const double* gv,
+                              const double* gprim, const double* gx_list, const double* gv_list, const double* gprim_list,
+                              int normalize, double* gx0, double* gv0, double* gprim0, double* gactions, double* gk,
+                              double* gmu, long* flips, int nthreads) {
+  const auto& tb = h->td;
+  const auto& pr = h->pd;
+  const int P = tb.P, S = pr.substeps;
+  const size_t rec = (size_t)P * 6 + 8;
+  std::vector<long> nflip(B, 0);
+#pragma omp parallel for num_threads(nthreads) schedule(static)
+  for (int b = 0; b < B; ++b) {
+    std::vector<float> ck((size_t)TT * S * rec);
+    std::vector<uint8_t> gr((size_t)TT * S * 2 * P);
+    std::vector<float> a1((size_t)TT * 8);
+    {
+      std::vector<float> xo(P * 3), vo(P * 3);
+      float po[8];
+      for (int t = 0; t < TT; ++t) std::memcpy(&a1[(size_t)t * 8], actions + ((size_t)t * B + b) * 8, sizeof(float) * 8);
+      rollout_fwd<float>(h, 1, TT, x0 + (size_t)b * P * 3, v0 + (size_t)b * P * 3, prim0 + b * 8, k + b, mu + b, a1.data(),
+                         xo.data(), vo.data(), po, nullptr, nullptr, nullptr, gr.data(), ck.data(), 1);
+    }
+    std::vector<double> cgx(gx + (size_t)b * P * 3, gx + (size_t)(b + 1) * P * 3), cgv(gv + (size_t)b * P * 3, gv + (size_t)(b + 1) * P * 3);
+    double cgp[8];
+    std::memcpy(cgp, gprim + b * 8, sizeof(cgp));
+    double ak = 0, amu = 0;
+    const double kb = k[b], mub = mu[b];
+    std::vector<double> scratch, c64(rec);
+    for (int t = TT - 1; t >= 0; --t) {
+      if (gx_list) for (int i = 0; i < P * 3; ++i) cgx[i] += gx_list[((size_t)t * B + b) * P * 3 + i];
+      if (gv_list) for (int i = 0; i < P * 3; ++i) cgv[i] += gv_list[((size_t)t * B + b) * P * 3 + i];
+      if (gprim_list) for (int i = 0; i < 8; ++i) cgp[i] += gprim_list[((size_t)t * B + b) * 8 + i];
+      float act32[8];
+      macro_action(&a1[(size_t)t * 8], act32);   // the macro action the f32 forward applied, then exactly in f64
+      double act[8], gact[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+      for (int i = 0; i < 8; ++i) act[i] = act32[i];
+      for (int s = S - 1; s >= 0; --s) {
+        const float* c = ck.data() + ((size_t)t * S + s) * rec;
+        for (size_t i = 0; i < rec; ++i) c64[i] = c[i];
+        const uint8_t* g0 = gr.data() + ((size_t)t * S + s) * 2 * P;
+        cloth_substep_bwd(tb, pr, normalize != 0, kb, mub, c64.data(), c64.data() + P * 3, c64.data() + P * 6, act, cgx.data(),
+                          cgv.data(), cgp, gact, &ak, &amu, scratch, g0, g0 + P, &nflip[b]);
+      }
+      double* ga = gactions + ((size_t)t * B + b) * 8;
+      for (int g = 0; g < 2; ++g) {
+        for (int c3 = 0; c3 < 3; ++c3) {
+          const double a = a1[(size_t)t * 8 + g * 4 + c3];
+          ga[g * 4 + c3] = gact[g * 4 + c3] * (1.0 / 50.0) * clip_grad(a, -2.0, 2.0);
+        }
+        ga[g * 4 + 3] = gact[g * 4 + 3];
+      }
+    }
+    std::memcpy(gx0 + (size_t)b * P * 3, cgx.data(), sizeof(double) * P * 3);
+    std::memcpy(gv0 + (size_t)b * P * 3, cgv.data(), sizeof(double) * P * 3);
+    std::memcpy(gprim0 + b * 8, cgp, sizeof(cgp));
+    gk[b] = ak;
+    gmu[b] = amu;
+  }
+  if (flips) {
+    *flips = 0;
+    for (int b = 0; b < B; ++b) *flips += nflip[b];
+  }
+}
+
 extern "C" {
 
 void* oc_cloth_create(int N, const uint8_t* mask, double gravity, double dt, double damp_f32, double damp_f64,
@@ -165,5 +234,14 @@ void oc_cloth_tables(void* h, int* nbr, float* L0) {
 DEFINE(f32, float)
 DEFINE(f64, double)
 #undef DEFINE
+
+void oc_cloth_rollout_bwd_mixed(void* h, int B, int TT, const float* x0, const float* v0, const float* prim0, const float* k,
+                                const float* mu, const float* actions, const double* gx, const double* gv, const double* gprim,
+                                const double* gx_list, const double* gv_list, const double* gprim_list, int normalize,
+                                double* gx0, double* gv0, double* gprim0, double* gactions, double* gk, double* gmu,
+                                long* flips, int nthreads) {
+  rollout_bwd_mixed((OcCloth*)h, B, TT, x0, v0, prim0, k, mu, actions, gx, gv, gprim, gx_list, gv_list, gprim_list, normalize,
+                    gx0, gv0, gprim0, gactions, gk, gmu, flips, nthreads);
+}
 
 }  // extern "C"

@@ -245,7 +245,8 @@ inline void norm_grad_bwd(T* g, int n, T n_mask) {  // :189-194
 template <class T>
 void cloth_substep_bwd(const ClothTables<T>& tb, const ClothParams<T>& pr, bool normalize, T k, T mu, const T* x,
                        const T* v, const T* prim, const T* act, T* gx, T* gv, T* gprim, T* gact, T* gk, T* gmu,
-                       std::vector<T>& scratch) {
+                       std::vector<T>& scratch, const uint8_t* force_m0 = nullptr, const uint8_t* force_m1 = nullptr,
+                       long* flips = nullptr) {
   const int P = tb.P;
   const T eps = pr.small_num;
   const T inf = std::numeric_limits<T>::infinity();
@@ -299,6 +300,13 @@ void cloth_substep_bwd(const ClothTables<T>& tb, const ClothParams<T>& pr, bool 
       T d[3] = {xx[0] - ps[0], xx[1] - ps[1], xx[2] - ps[2]};
       T dist = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
       bool m = dist <= ps[3];
+      // force_m0/m1 (optional): the grasp sets a forward in another precision recorded; this sweep follows them and
+      // counts the particles where its own test disagrees (rollout_bwd_mixed)
+      const uint8_t* fm = (g == 0) ? force_m0 : force_m1;
+      if (fm) {
+        if (flips && (fm[i] != 0) != m) ++*flips;
+        m = fm[i] != 0;
+      }
       (g == 0 ? m0 : m1)[i] = m ? T(1) : T(0);
       if (m) {
         T suction = ac[3];

@@ -116,7 +116,16 @@ class ClothOracle:
         return out
 
     def rollout_bwd(self, x0, v0, prim0, k, mu, actions, gx, gv, gprim, gx_list=None, gv_list=None,
-                    gprim_list=None, normalize=True, nthreads=1):
+                    gprim_list=None, normalize=True, nthreads=1, adjoint_dtype=None):
+        """Adjoint of rollout_fwd.  adjoint_dtype=None: forward and adjoint in x0's dtype.  adjoint_dtype=np.float32: both in f32.
+        adjoint_dtype=np.float64: the forward in f32 (the inputs must hold f32 values), the adjoint of that f32 trajectory in f64
+        (oc_cloth_rollout_bwd_mixed); the result then also carries `flips`, the grasp tests the f64 sweep decided otherwise
+        (it follows the f32 forward's decisions)."""
+        if adjoint_dtype is not None and np.dtype(adjoint_dtype) == np.float64:
+            return self._rollout_bwd_mixed(x0, v0, prim0, k, mu, actions, gx, gv, gprim, gx_list, gv_list, gprim_list,
+                                           normalize, nthreads)
+        if adjoint_dtype is not None:
+            x0 = np.asarray(x0, dtype=adjoint_dtype)
         dt = x0.dtype
         B, P = x0.shape[0], self.P
         T = actions.shape[0]
@@ -131,6 +140,29 @@ class ClothOracle:
             _p(gx), _p(gv), _p(gprim), _p(gx_list), _p(gv_list), _p(gprim_list), C.c_int(int(normalize)),
             _p(gx0), _p(gv0), _p(gp0), _p(ga), _p(gk), _p(gmu), C.c_int(nthreads))
         return dict(gx=gx0, gv=gv0, gprim=gp0, gactions=ga, gk=gk, gmu=gmu)
+
+    def _rollout_bwd_mixed(self, x0, v0, prim0, k, mu, actions, gx, gv, gprim, gx_list, gv_list, gprim_list, normalize, nthreads):
+        B, P = x0.shape[0], self.P
+        T = actions.shape[0]
+
+        def f32(a):
+            a32 = np.ascontiguousarray(a, dtype=np.float32)
+            assert np.array_equal(a32, np.asarray(a)), "the f32 forward needs inputs that hold f32 values"
+            return a32
+
+        f64 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+        x0, v0, prim0, k, mu, actions = map(f32, (x0, v0, prim0, k, mu, actions))
+        gx, gv, gprim, gx_list, gv_list, gprim_list = map(f64, (gx, gv, gprim, gx_list, gv_list, gprim_list))
+        assert x0.shape == (B, P, 3) and prim0.shape == (B, 2, 4) and actions.shape == (T, B, 8)
+        gx0, gv0, gp0 = (np.empty(a.shape, np.float64) for a in (x0, v0, prim0))
+        ga = np.empty((T, B, 8), np.float64)
+        gk, gmu = np.empty((B,), np.float64), np.empty((B,), np.float64)
+        flips = C.c_long(0)
+        lib().oc_cloth_rollout_bwd_mixed(
+            self.h, C.c_int(B), C.c_int(T), _p(x0), _p(v0), _p(prim0), _p(k), _p(mu), _p(actions),
+            _p(gx), _p(gv), _p(gprim), _p(gx_list), _p(gv_list), _p(gprim_list), C.c_int(int(normalize)),
+            _p(gx0), _p(gv0), _p(gp0), _p(ga), _p(gk), _p(gmu), C.byref(flips), C.c_int(nthreads))
+        return dict(gx=gx0, gv=gv0, gprim=gp0, gactions=ga, gk=gk, gmu=gmu, flips=int(flips.value))
 
 
 class MpmOracle:

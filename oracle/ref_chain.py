@@ -1,0 +1,296 @@
+"""ORACLE reference chain (test infrastructure only): the APG gradient of the cloth envs, restated on the CPU oracle.
+
+A cloth env's step_diff and the APG loss written out again, independently of ClothEnv.step_diff, APG.loss and the fused
+glue, so that tests can compare the gradient the product computes end to end with one from a plain implementation:
+    rollout       ClothRolloutFn: forward ClothOracle.rollout_fwd (f32, the env's operation order), backward
+                  ClothOracle.rollout_bwd with the adjoint in f64 (R64: the f32 trajectory's adjoint, oc_cloth_rollout_bwd_mixed)
+                  or f32 (R32)
+    step_diff     cloth_env.py:205-228   pick-and-place expansion :134-173 (the XLA reciprocal rule for / 3 and / 20),
+                  contact distance :206-209, chamfer util.py:138-153, e ** (-10 d), the aux term, 0.99 ** cur_step, get_obs :94-132
+                  (cloth_env_para.py:130 for the stiffness column; fold_cloth_tshirt_env.py:69-111 for every tenth particle)
+    APG loss      apg.py:177-215   policy MLP, NormalTanhDistribution sample, sigmoid squash, -mean(rewards)
+
+Forward values are f32 and bit-identical to what the HIP env computes from the same inputs: every quantity that feeds the
+rollout (macro actions, state) is computed in f32 with the kernels' arithmetic, and the gradient flows through an expression of
+the same value in the chain's own dtype (`value.detach() + (expr - expr.detach())`).  Discrete choices (the argmins) are made
+on the f32 distances, as jnp makes them; the continuous arithmetic after them is in the chain's dtype.
+
+`mutate` (a set of names) plants one of the mistakes the GPU tests must be able to see; tests/test_ref_chain.py measures how far
+each moves the gradient:
+    contact_grad     the contact term's gradient dropped
+    discount         0.99 ** (cur_step - 1): the discount of the step before
+    prim0_grad       the expansion's cotangent on primitive0 zeroed
+    chamfer_yx_grad  the goal -> cloth chamfer direction's gradient dropped
+    obs_detach       the observation -> policy path cut
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+import torch.nn.functional as Fn
+
+from .pyoracle import ClothOracle
+
+# `/ 3`, `/ 20` as XLA executes them under jit: multiplication by the f32 reciprocal (cloth_env.py:148-163)
+_R3 = np.float32(1) / np.float32(3)
+_R20 = np.float32(1) / np.float32(20)
+MUTATIONS = ("contact_grad", "discount", "prim0_grad", "chamfer_yx_grad", "obs_detach")
+# the bar of tests/test_grad_chain_gpu.py, per compared tensor:  |HIP - R64|max <= KAPPA * |R32 - R64|max + REL_FLOOR * |R64|max
+# (KAPPA: twice the largest ratio |HIP - R64| / |R32 - R64| measured on the MI355X, 1.92; that file's docstring lists them)
+KAPPA = 4.0
+REL_FLOOR = 1e-6
+
+
+def bar(r64, r32):
+    """what the product may differ from R64 by (see KAPPA)"""
+    r64, r32 = (np.asarray(t, np.float64) for t in (r64, r32))
+    return KAPPA * np.abs(r32 - r64).max() + REL_FLOOR * np.abs(r64).max()
+
+
+def _f32(t):
+    """the f32 values of a tensor that must hold f32 values (the forward of the chain runs on them)"""
+    a = t.detach().cpu().numpy()
+    a32 = a.astype(np.float32)
+    assert np.array_equal(a32, a), "a forward value of the reference chain is not an f32 value"
+    return a32
+
+
+def _st(value32, expr):
+    """value32's values, expr's gradient"""
+    v = torch.as_tensor(value32, dtype=expr.dtype)
+    return v + (expr - expr.detach())
+
+
+class ClothRolloutFn(torch.autograd.Function):
+    """lax.scan(step_jax) over the macro actions on the CPU oracle: (x, v, prim [B,2,4], k, mu, actions [T,B,8]) ->
+    (x, v, prim[, x_list, v_list, prim_list]).  The adjoint runs in the dtype of x (f64: along the f32 trajectory)."""
+
+    @staticmethod
+    def forward(ctx, ref, x, v, prim, k, mu, actions):
+        dt = x.dtype
+        if ref.forward_f64:     # finite-difference checks only: forward and adjoint both in f64
+            ins = [t.detach().numpy().astype(np.float64) for t in (x, v, prim, k, mu, actions)]
+        else:
+            ins = [_f32(t) for t in (x, v, prim, k, mu, actions)]
+        o = ref.orc.rollout_fwd(*ins, want_lists=ref.want_lists, nthreads=ref.nthreads)
+        ctx.ref, ctx.ins, ctx.dt = ref, ins, dt
+        keys = ("x", "v", "prim") + (("x_list", "v_list", "prim_list") if ref.want_lists else ())
+        return tuple(torch.from_numpy(o[q]).to(dt) for q in keys)
+
+    @staticmethod
+    def backward(ctx, *g):
+        ref, dt = ctx.ref, ctx.dt
+        npdt = np.float64 if dt == torch.float64 else np.float32
+        x, v, prim, k, mu, actions = ctx.ins
+        z = lambda t, like: np.zeros(like.shape, npdt) if t is None else t.detach().numpy().astype(npdt)
+        gx, gv, gp = z(g[0], x), z(g[1], v), z(g[2], prim)
+        T = actions.shape[0]
+        lists = [None, None, None]
+        if ref.want_lists:
+            lists = [None if t is None else t.detach().numpy().astype(npdt) for t in g[3:6]]
+        r = ref.orc.rollout_bwd(x, v, prim, k, mu, actions, gx, gv, gp, *lists, normalize=ref.normalize,
+                                nthreads=ref.nthreads, adjoint_dtype=None if ref.forward_f64 else npdt)
+        if "flips" in r:
+            ref.flips += r["flips"]
+        t = lambda q: torch.from_numpy(np.ascontiguousarray(r[q])).to(dt)
+        return None, t("gx"), t("gv"), t("gprim"), t("gk"), t("gmu"), t("gactions")
+
+
+class ClothRefEnv:
+    """A cloth env's step_diff on the CPU oracle in the chain's dtype (torch.float64: R64, torch.float32: R32).
+    State: dict x [B,P,3], v, primitive0 [B,4], primitive1, stiffness [B], mu [B] (tensors of the chain's dtype holding f32
+    values) and cur_step (int numpy [B])."""
+
+    def __init__(self, conf, mask, goal, max_steps, dtype=torch.float64, aux_reward=True, eval_min_max_stiff=None,
+                 obs_stride=1, order=2, substeps=None, normalize=True, use_substep_obs=None, nthreads=1, mutate=()):
+        self.dtype = dtype
+        self.conf = conf
+        self.substeps = int(getattr(conf, "substeps", 50) if substeps is None else substeps)
+        self.orc = ClothOracle(np.asarray(mask), N=conf.N, gravity=conf.gravity, damping=conf.damping, dt=conf.dt,
+                               max_v=conf.max_v, small_num=conf.small_num, substeps=self.substeps, order=order)
+        self.goal32 = np.ascontiguousarray(goal, dtype=np.float32)
+        self.goal = torch.from_numpy(self.goal32).to(dtype)
+        self.max_steps, self.aux_reward = max_steps, aux_reward
+        self.eval_min_max_stiff = eval_min_max_stiff
+        self.obs_stride = obs_stride
+        self.normalize = normalize
+        self.want_lists = bool(conf.use_substep_obs if use_substep_obs is None else use_substep_obs)
+        self.nthreads = nthreads
+        self.mutate = set(mutate)
+        assert self.mutate <= set(MUTATIONS), self.mutate
+        self.forward_f64 = False    # ClothRolloutFn's forward in f64 too (finite-difference checks of its wiring)
+        self.flips = 0              # grasp decisions the f64 adjoint sweep saw otherwise (it follows the f32 forward)
+        self.check_pnp = None       # optional callback (actions32, primitive0_32, x32) -> (macro, contact) of the product, compared bit for bit
+
+    @classmethod
+    def from_env(cls, env, dtype=torch.float64, nthreads=1, mutate=()):
+        """the reference of a constructed ClothEnv (its conf, mask, goal and kernel order)"""
+        sim = env.simulator
+        return cls(env.conf, np.asarray(env.cloth_mask), env.goal.cpu().numpy(), env.max_steps, dtype=dtype, aux_reward=env.aux_reward,
+                   eval_min_max_stiff=env.eval_min_max_stiff, obs_stride=10 if env.conf.task == "fold_tshirt" else 1,
+                   order=1 if sim.mode in (1, 3) else 2, substeps=sim.substeps, normalize=sim.normalize_grad, nthreads=nthreads,
+                   mutate=mutate)
+
+    def state_from(self, st, **leaves):
+        """a reference state from a ClothState (device tensors); `leaves` replaces fields by tensors of the chain's dtype"""
+        c = lambda t: torch.from_numpy(t.detach().cpu().numpy()).to(self.dtype)
+        s = dict(x=c(st.x), v=c(st.v), primitive0=c(st.primitive0), primitive1=c(st.primitive1),
+                 stiffness=c(st.stiffness.to(torch.float32)), mu=c(st.mu), cur_step=st.cur_step.cpu().numpy().astype(np.int64))
+        s.update(leaves)
+        return s
+
+    # -- get_obs (cloth_env.py:94-132) -----------------------------------------------------------------------------------
+    def get_obs(self, x, primitive0, primitive1, stiffness):
+        lead = x.shape[:-2]
+        parts = [x[..., ::self.obs_stride, :].reshape(lead + (-1,)), primitive0, primitive1]
+        if self.eval_min_max_stiff is not None:      # cloth_env_para.py:130
+            lo, hi = float(self.eval_min_max_stiff[0]), float(self.eval_min_max_stiff[1])
+            parts.append((stiffness[..., None] - lo) / (hi - lo))
+        return torch.cat(parts, -1)
+
+    # -- get_pnp_actions (cloth_env.py:134-173) and contact_distance (:206-209) --------------------------------------------
+    def pnp(self, actions, primitive0, x):
+        B = actions.shape[0]
+        a32, p32, x32 = _f32(actions), _f32(primitive0), _f32(x)
+        # f32 values, the kernels' arithmetic
+        m32 = np.zeros((40, B, 8), np.float32)
+        m32[0:3, :, 0] = (a32[:, 0] - p32[:, 0]) * _R3
+        m32[0:3, :, 1] = (np.float32(0) - p32[:, 1]) * _R3
+        m32[0:3, :, 2] = (a32[:, 2] - p32[:, 2]) * _R3
+        m32[0:3, :, 3] = 1
+        m32[3:13, :, 1] = np.float32(0.06) / np.float32(10)
+        m32[13:33, :, 0] = (a32[:, 3] - a32[:, 0]) * _R20
+        m32[13:33, :, 2] = (a32[:, 5] - a32[:, 2]) * _R20
+        m32[33:40, :, 3] = 1
+        d = a32[:, None, :3] - x32
+        s32 = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+        idx = np.argmin(s32, 1)                                         # the first minimum
+        c32 = np.sqrt(s32[np.arange(B), idx])
+        if self.check_pnp is not None:
+            macro_p, contact_p = self.check_pnp(a32, p32, x32)
+            assert np.array_equal(macro_p, m32), "macro actions differ from the product's"
+            assert np.array_equal(contact_p, c32), "contact distance differs from the product's"
+        # the same expressions in the chain's dtype, for the gradient
+        p0 = primitive0.detach() if "prim0_grad" in self.mutate else primitive0
+        z = torch.zeros_like(actions[:, 0])
+        down = torch.stack([(actions[:, 0] - p0[:, 0]) * float(_R3), (z - p0[:, 1]) * float(_R3),
+                            (actions[:, 2] - p0[:, 2]) * float(_R3)], -1)
+        move = torch.stack([(actions[:, 3] - actions[:, 0]) * float(_R20), z, (actions[:, 5] - actions[:, 2]) * float(_R20)], -1)
+        g = torch.cat([down[None].expand(3, B, 3), torch.zeros((10, B, 3), dtype=actions.dtype),
+                       move[None].expand(20, B, 3), torch.zeros((7, B, 3), dtype=actions.dtype)], 0)
+        g = torch.cat([g, torch.zeros((40, B, 5), dtype=actions.dtype)], -1)
+        macro = _st(m32, g)
+        xi = x[torch.arange(B), torch.as_tensor(idx)]
+        contact = torch.sqrt(((actions[:, :3] - xi) ** 2).sum(-1))
+        return macro, contact
+
+    # -- calc_chamfer (util.py:138-153) ------------------------------------------------------------------------------------
+    def chamfer(self, x):
+        x32, y32 = _f32(x), self.goal32
+        B = x32.shape[0]
+        ixy, iyx = [], []
+        for b in range(B):
+            d = x32[b][:, None, :] - y32[None]
+            m = ((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]) / np.float32(3)
+            ixy.append(np.argmin(m, 1))
+            iyx.append(np.argmin(m, 0))
+        ixy, iyx = torch.as_tensor(np.stack(ixy)), torch.as_tensor(np.stack(iyx))
+        bi = torch.arange(B)[:, None]
+        y = self.goal
+        x2y = torch.sqrt(((x - y[ixy]) ** 2).mean(-1)).mean(1)
+        xs = x.detach() if "chamfer_yx_grad" in self.mutate else x
+        y2x = torch.sqrt(((xs[bi, iyx] - y[None]) ** 2).mean(-1)).mean(1)
+        return y2x + x2y
+
+    # -- step_diff (cloth_env.py:201-231) ----------------------------------------------------------------------------------
+    def step(self, actions, s):
+        """-> (obs, reward, new state, obs_list)"""
+        macro, contact = self.pnp(actions, s["primitive0"], s["x"])
+        prim = torch.stack([s["primitive0"], s["primitive1"]], 1)
+        out = ClothRolloutFn.apply(self, s["x"], s["v"], prim, s["stiffness"], s["mu"], macro)
+        x, v, p = out[:3]
+        cur = s["cur_step"] + 1
+        new = dict(x=x, v=v, primitive0=p[:, 0], primitive1=p[:, 1], stiffness=s["stiffness"], mu=s["mu"], cur_step=cur)
+        obs = self.get_obs(x, p[:, 0], p[:, 1], s["stiffness"])
+        obs_list = None
+        if self.want_lists:
+            xl, pl = out[3], out[5]
+            obs_list = self.get_obs(xl, pl[:, :, 0], pl[:, :, 1], s["stiffness"][None].expand(xl.shape[0], -1))
+        reward = torch.exp(self.chamfer(x) * -10.0)
+        if self.aux_reward:
+            reward = reward + torch.exp(-(contact.detach() if "contact_grad" in self.mutate else contact))
+        n = cur - 1 if "discount" in self.mutate else cur
+        reward = reward * torch.as_tensor(0.99 ** n.astype(np.float64), dtype=self.dtype)
+        return obs, reward, new, obs_list
+
+
+# -- the APG loss (apg.py:177-215) ---------------------------------------------------------------------------------------
+class PolicyRef:
+    """the policy MLP (apg.py:353-358, swish between Dense layers) on a copy of the parameters in `dtype`"""
+
+    def __init__(self, params, dtype):
+        self.params = [torch.tensor(p.detach().cpu().numpy(), dtype=dtype, requires_grad=True) for p in params]
+
+    def __call__(self, obs):
+        h = obs
+        n = len(self.params) // 2
+        for i in range(n):
+            h = Fn.linear(h, self.params[2 * i], self.params[2 * i + 1])
+            if i < n - 1:
+                h = h * torch.sigmoid(h)
+        return h
+
+
+def squashed_action(logits, eps, min_std=0.001):
+    """sigmoid(NormalTanhDistribution.sample) (apg.py:98-100, :184-186): tanh(loc + (softplus(raw) + min_std) * eps)"""
+    loc, raw = torch.chunk(logits, 2, dim=-1)
+    return torch.sigmoid(torch.tanh(loc + (Fn.softplus(raw) + min_std) * eps))
+
+
+def apg_loss(env_ref, policy, state, noise, action_values=None):
+    """-mean(rewards) of len(noise) scanned do_one_step calls.  action_values[t] (f32 [B,6]), when given, are the values the
+    actions take (the product's, so that the forward is the product's bit for bit); the gradient flows through the
+    reference policy's own expression.  Without them the chain's action values are used (they must be f32 values)."""
+    rewards, acts = [], []
+    s = state
+    for t in range(len(noise)):
+        obs = env_ref.get_obs(s["x"], s["primitive0"], s["primitive1"], s["stiffness"])
+        if "obs_detach" in env_ref.mutate:
+            obs = obs.detach()
+        a = squashed_action(policy(obs), torch.as_tensor(np.asarray(noise[t]), dtype=env_ref.dtype))
+        if action_values is not None:
+            a = _st(np.asarray(action_values[t], np.float32), a)
+        acts.append(a)
+        _, reward, s, _ = env_ref.step(a, s)
+        rewards.append(reward)
+    rewards = torch.stack(rewards)
+    return -rewards.mean(), rewards, acts
+
+
+def adam_first_step(params, grads, lr, max_gradient_norm, b1=0.9, b2=0.999, eps=1e-8):
+    """clip_by_global_norm, then the first optax.adam step from zero moments (apg.py:217-267): the clipped gradient and the
+    parameter update"""
+    flat = torch.cat([g.reshape(-1) for g in grads])
+    flat = torch.nan_to_num(flat)
+    nrm = torch.linalg.vector_norm(flat)
+    clipped = flat * (max_gradient_norm / nrm if nrm >= max_gradient_norm else 1.0)
+    m = (1 - b1) * clipped / (1 - b1)
+    v = (1 - b2) * clipped * clipped / (1 - b2)
+    return clipped, -lr * m / (torch.sqrt(v) + eps)
+
+
+def cloth_reset_state(conf, mask, B, key, dtype=torch.float64):
+    """ClothEnv.reset without a GPU (cloth_simulator.py:339-364, cloth_env.py:181-185): the flat lattice, shifted in x and z by
+    normal(split(key)[0], 2) * 0.05 in f32"""
+    from unidom_amd.utils import prng
+    N = conf.N
+    c = 1.0 / N
+    ii, jj = np.nonzero(np.asarray(mask))
+    x = np.stack([ii * c, np.zeros_like(ii, dtype=np.float64), (N - jj) * c], -1).astype(np.float32)
+    k = prng.split(np.asarray(key, dtype=np.uint32))[0]
+    shift = prng.normal(k, 2) * np.float32(0.05)
+    x[:, 0] += np.float32(shift[0])
+    x[:, 2] += np.float32(shift[1])
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(np.repeat(np.asarray(a, np.float32)[None], B, 0))).to(dtype)
+    return dict(x=t(x), v=t(np.zeros_like(x)), primitive0=t([0.5, 0.5, 0.5, 0.01]), primitive1=t([1.0, 1.0, 1.0, 0.01]),
+                stiffness=t(np.float32(conf.stiffness)), mu=t(np.float32(conf.mu)), cur_step=np.zeros(B, np.int64))

@@ -8,8 +8,10 @@
 // second half of this file.
 //   chamfer        core/utils/util.py:138-153     d(p,q) = sqrt(mean_xyz((x_p - y_q)^2)); mean_p min_q + mean_q min_p
 //   pnp / contact  core/envs/basic/cloth_env.py:134-173 (get_pnp_actions), :206-209 (contact_distance)
-// The backward kernels return what jax.grad / torch.autograd return for the same expressions: the minimum passes its
-// cotangent to one argmin (the first on ties), sqrt's derivative at 0 is left as the 0/0 it is in the reference.
+// The backward kernels return what jax.grad returns for the same expressions away from ties: the minimum passes its cotangent
+// to one argmin, sqrt's derivative at 0 is left as the 0/0 it is in the reference.  On a tie they differ: the minimum here is
+// taken over the squared distances and the whole cotangent goes to the first index attaining it (torch.min's rule), while
+// JAX's reduce_min JVP splits it evenly over every position equal to the minimum of the post-sqrt distances.
 #include "common.h"
 
 namespace ud {
