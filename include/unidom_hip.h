@@ -71,12 +71,16 @@ typedef struct {
                     * 3: forward in the reference's literal f32 operation order (mode 1's forward kernel: k*r/len*(len-L0)/L0,
                     *    cloth_simulator.py:264-268, and the friction block :281-306 as written; bit-identical to the CPU
                     *    restatement of THAT order) + the restructured adjoint of modes 0 / 2 (it reads the same checkpoint
-                    *    records and re-derives the grasp sets from them).  Bodies of at most 512 particles
-                    *    (UD_ERR_UNSUPPORTED above).
+                    *    records and re-derives the grasp sets from them).  Bodies of at most 512 particles or of more
+                    *    than 1024 (UD_ERR_UNSUPPORTED for 513-1024).
                     * Bodies above 1024 particles: modes 0 / 2 run the v2-order forward and the restructured adjoint on
                     *    SEVERAL workgroups per env (512 particles each, halo positions / force cotangents / block sums handed
-                    *    over through HBM every substep; forward still bit-identical to the v2 restatement); mode 1 runs the
-                    *    reference-order kernels on one 1024-lane workgroup per env. */
+                    *    over through HBM every substep; forward still bit-identical to the v2 restatement); mode 3 runs the
+                    *    reference-order forward on the same parts and hand-off (bit-identical to the reference-order
+                    *    restatement) and the same restructured adjoint; mode 1 runs the reference-order kernels on one
+                    *    1024-lane workgroup per env.  Where the several-workgroup kernels do not apply (one_workgroup_per_env,
+                    *    a spring spanning more than 256 particle indices, more parts than CUs per XCD) modes 0 / 2 / 3 run
+                    *    mode 1's one-workgroup kernels too: reference order. */
   int max_envs;    /* the largest B any call on this handle will pass (>= 1): handle-owned scratch (bodies above 1024 particles: the
                     * several-workgroup kernels' hand-off arena, or the one-workgroup adjoint's parking area) is allocated in
                     * ud_cloth_create for this many envs; a call with more returns UD_ERR_INVALID */

@@ -730,8 +730,9 @@ struct ud_cloth {
 };
 
 // Several workgroups per env when the body qualifies (halo <= CL_HMAX, the parts of one env fit on the chip) and the caller
-// did not ask for the reference-order kernels (mode 1).  A call is cut into launches of cloth_cluster_envs() envs so that
-// every workgroup of a launch is resident at once (cloth_cluster.h, "Progress").
+// did not ask for the literal reference-order kernels (mode 1).  Mode 3 runs its own forward there (cloth_cluster_ref.hip, reference
+// order) and the same adjoint.  A call is cut into launches of cloth_cluster_envs() envs so that every workgroup of a launch is
+// resident at once (cloth_cluster.h, "Progress").  A body that does not qualify runs cloth_big_fwd / bwd_kernel: reference order.
 // ud_cloth_conf.one_workgroup_per_env != 0 (fixed at create; diagnostics and tests) keeps the one-workgroup kernels.
 static bool cloth_use_cluster(const ud_cloth* h, int B) {
   if (h->c.Pp <= 1024 || h->cl_H == 0 || h->mode == 1 || h->cl_W > h->n_cu / 8) return false;   // the parts of an env share an XCD (cl_decode)
@@ -805,8 +806,8 @@ int ud_cloth_create(const ud_cloth_conf* conf, const uint8_t* mask, ud_cloth** o
   }
   h->mode = conf->mode;
   if (h->mode < 0 || h->mode > 3) { ud::set_error("ud_cloth_create: mode must be 0, 1, 2 or 3"); delete h; return UD_ERR_INVALID; }
-  if (h->mode == 3 && Pp > 512) {   // the restructured adjoint of bodies above 512 particles belongs to the several-workgroup (v2-order) kernels
-    ud::set_error("ud_cloth_create: mode 3 (reference-order forward + restructured adjoint) covers bodies of at most 512 particles, P=%d", P);
+  if (h->mode == 3 && Pp > 512 && Pp <= 1024) {   // no restructured adjoint for 513-1024 particles (one workgroup, two particles per lane)
+    ud::set_error("ud_cloth_create: mode 3 (reference-order forward + restructured adjoint) covers bodies of at most 512 or more than 1024 particles, P=%d", P);
     delete h; return UD_ERR_UNSUPPORTED;
   }
   if (conf->max_envs < 1) { ud::set_error("ud_cloth_create: max_envs = %d (handle-owned scratch is sized at create: give the largest B any call will pass)", conf->max_envs); delete h; return UD_ERR_INVALID; }
@@ -905,7 +906,10 @@ int ud_cloth_rollout_fwd(ud_cloth* h, int B, int T, const float* x, const float*
       const int rc = cloth_cluster_arena(h, std::min(per, B - b0), (hipStream_t)stream, &q);
       if (rc != UD_OK) return rc;
       q.b0 = b0;
-      ud::cloth_launch_fwd_cluster(a, q, (hipStream_t)stream);
+      if (h->mode == 3)   // reference order; constants outside cloth_ref.hip's checks -> every wave on the literal code
+        ud::cloth_launch_fwd_cluster_ref(a, q, ud::cloth_ref_consts_ok(h->c) ? 1 : 0, (hipStream_t)stream);
+      else
+        ud::cloth_launch_fwd_cluster(a, q, (hipStream_t)stream);
     }
   } else if (h->c.Pp > 1024)
     hipLaunchKernelGGL(ud::cloth_big_fwd_kernel, dim3(B), dim3(UD_BIG_T), (size_t)9 * h->c.Pp * sizeof(float), (hipStream_t)stream, a);

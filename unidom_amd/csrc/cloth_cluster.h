@@ -79,6 +79,7 @@ __device__ __forceinline__ bool cl_poll3(const cl_granule* p, size_t plane, unsi
 }
 
 void cloth_launch_fwd_cluster(const ClothFwdArgs& a, const ClusterArgs& q, hipStream_t stream);
+void cloth_launch_fwd_cluster_ref(const ClothFwdArgs& a, const ClusterArgs& q, int fast, hipStream_t stream);   // mode 3 (cloth_cluster_ref.hip)
 void cloth_launch_bwd_cluster(const ClothBwdArgs& a, const ClusterArgs& q, hipStream_t stream);
 
 }  // namespace ud
