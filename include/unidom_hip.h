@@ -73,6 +73,10 @@ typedef struct {
                     *    restatement of THAT order) + the restructured adjoint of modes 0 / 2 (it reads the same checkpoint
                     *    records and re-derives the grasp sets from them).  Bodies of at most 512 particles or of more
                     *    than 1024 (UD_ERR_UNSUPPORTED for 513-1024).
+                    * Bodies of 513-1024 particles (padded to whole waves: 512 < Pp <= 1024) have mode 1's kernels only, one
+                    *    workgroup of Pp lanes per env: modes 0 and 2 run them as well, so THERE THE FORWARD IS IN THE REFERENCE'S
+                    *    LITERAL ORDER (bit-identical to the reference-order restatement, not to v2's) and the adjoint is the
+                    *    literal six-reduction one; mode 3 is refused.
                     * Bodies above 1024 particles: modes 0 / 2 run the v2-order forward and the restructured adjoint on
                     *    SEVERAL workgroups per env (512 particles each, halo positions / force cotangents / block sums handed
                     *    over through HBM every substep; forward still bit-identical to the v2 restatement); mode 3 runs the
@@ -90,7 +94,8 @@ typedef struct {
 
 /* mask: host pointer, N*N bytes, row-major, non-zero = cloth particle (create_cloth_mask,
  * fold_cloth1_env.py:48-53).  Particle order = row-major nonzero(mask) (cloth_simulator.py:52).
- * Limits: 1 <= P <= 4096 (P <= 1024: one workgroup per env, one particle per lane; above: ceil(P / 512) workgroups per
+ * Limits: 1 <= P <= 4096 (P <= 1024: one workgroup per env, one particle per lane -- the kernels of the handle's mode up to 512
+ * particles, mode 1's reference-order forward and literal adjoint in modes 0 / 1 / 2 for 513-1024; above: ceil(P / 512) workgroups per
  * env, one particle per lane -- a call is cut into launches of ud_cloth_launch_envs() envs so that the workgroups that
  * wait for each other are resident together -- or, in mode 1 / when a spring spans more than 256 particle indices, one
  * workgroup per env with up to four particles per lane); the mask must not touch the lattice border

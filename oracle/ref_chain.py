@@ -124,11 +124,12 @@ class ClothRefEnv:
 
     @classmethod
     def from_env(cls, env, dtype=torch.float64, nthreads=1, mutate=()):
-        """the reference of a constructed ClothEnv (its conf, mask, goal and kernel order)"""
+        """the reference of a constructed ClothEnv (its conf, mask, goal and the operation order its handle really runs:
+        ClothSimulator.forward_order -- not the mode alone, bodies of 513-1024 particles run the reference order in every mode)"""
         sim = env.simulator
         return cls(env.conf, np.asarray(env.cloth_mask), env.goal.cpu().numpy(), env.max_steps, dtype=dtype, aux_reward=env.aux_reward,
                    eval_min_max_stiff=env.eval_min_max_stiff, obs_stride=10 if env.conf.task == "fold_tshirt" else 1,
-                   order=1 if sim.mode in (1, 3) else 2, substeps=sim.substeps, normalize=sim.normalize_grad, nthreads=nthreads,
+                   order=sim.forward_order, substeps=sim.substeps, normalize=sim.normalize_grad, nthreads=nthreads,
                    mutate=mutate)
 
     def state_from(self, st, **leaves):

@@ -135,7 +135,10 @@ class ClothSimulator:
         # formulas re-associated; bit-identical to the CPU restatement of the same order) + restructured adjoint, 1 forward
         # and adjoint in the reference's literal operation order, 2 fast-math v2 forward + restructured adjoint, 3 forward in
         # the reference's literal operation order (cloth_simulator.py:257-337 as written) + restructured adjoint (bodies of at most
-        # 512 particles, or of more than 1024: there on several workgroups per env like mode 0)
+        # 512 particles, or of more than 1024: there on several workgroups per env like mode 0).
+        # Bodies of 513-1024 particles (padded to whole waves: 512 < Pp <= 1024) have mode 1's kernels only: modes 0 and 2 run
+        # them too -- forward in the reference's literal order, NOT v2, and the literal adjoint -- and mode 3 is refused.
+        # `forward_order` reports the order a handle really runs.
         self.mode = int(getattr(conf, "kernel_mode", 0) if mode is None else mode)
         self.profile = None                  # bench.py: {"fwd": [...], "bwd": [...]} lists of (start, end) events
         self._suction_col = torch.tensor([[False, False, False, True] * 2], device=self.device)   # columns robot_step leaves unscaled
@@ -201,6 +204,29 @@ class ClothSimulator:
     def launch_envs(self, B=None):
         """envs per kernel launch of a call with B envs (ud_cloth_launch_envs)"""
         return int(_lib.lib().ud_cloth_launch_envs(self._h, C.c_int(self.batch_size if B is None else B)))
+
+    @property
+    def several_workgroups(self):
+        """whether this handle runs several workgroups per env: a launch then holds at most 8 * floor((CUs / 8) / parts) <= CUs
+        envs, so a call of more envs than any chip has CUs is cut exactly when it does"""
+        return self.launch_envs(1 << 20) < (1 << 20)
+
+    @property
+    def forward_order(self):
+        """The operation order of the forward this handle runs, as oracle.pyoracle.ClothOracle numbers them: 1 = the reference's
+        literal order, 2 = "v2" (mode 2: v2's structure with fast-math, bit-identical to neither).  The dispatch of
+        csrc/cloth.hip (ud_cloth_rollout_fwd) restated from the mode, the padded particle count Pp and whether several
+        workgroups per env are used:
+            Pp <= 512          modes 0 / 2: order 2; modes 1 / 3: order 1
+            512 < Pp <= 1024   order 1 in every mode (mode 1's kernels; mode 3 is refused at create)
+            Pp > 1024          several workgroups: mode 3 order 1, modes 0 / 2 order 2; one workgroup (mode 1,
+                               one_workgroup_per_env, a body that does not qualify): order 1"""
+        Pp = -(-self.n_particles // 64) * 64
+        if Pp > 1024:
+            return (1 if self.mode == 3 else 2) if self.several_workgroups else 1
+        if Pp > 512:
+            return 1
+        return 1 if self.mode in (1, 3) else 2
 
     # -- state helpers -------------------------------------------------------------------------------
     def reset_jax(self) -> ClothState:  # :339-364
