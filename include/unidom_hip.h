@@ -178,7 +178,8 @@ typedef struct {
                                 rematerialises the whole substep, mpm_simulator.py:332-359).  K > 0: the forward also
                                 checkpoints the active grid cells (32 B each) into a pool of K * n_particles records per
                                 substep on average, inside the caller's checkpoint (ud_mpm_ckpt_bytes grows accordingly),
-                                and the backward restores them.  A pool that runs out flags the env in status[] (1) */
+                                and the backward restores them.  A pool that runs out flags the env in status[] (1) and in a word
+                                of the checkpoint itself, which ud_mpm_step_bwd reads on the device under clip bit 2 */
   int sort_particles;        /* many-workgroup path only.  != 0: at every step the handle re-orders the particles by grid cell
                                 (Morton key) internally, for bodies whose particles come in no spatial order (uniformly
                                 sampled liquids, mpm_simulator.py:87-91); bodies above 8192 particles keep their order (the
@@ -231,7 +232,9 @@ void ud_mpm_destroy(ud_mpm* h);
 /* bytes of the checkpoint one ud_mpm_step_fwd call with B envs writes for its backward: the particle state of every substep; on
  * the many-workgroup path also the primitive rows, the spatial order, the grid-checkpoint pool and -- while B * n_particles is
  * below 100 000 (the regime where a launch waits for one wave's serial chain) -- the SVD factors of every substep's F, which
- * the backward reads instead of iterating again.  The layout is the library's; the same B must be passed to the backward */
+ * the backward reads instead of iterating again; with grid_ckpt_cells > 0 also one int per env beside the pool's record index, which the
+ * forward sets to non-zero exactly when it raises bit 0 of that env's status[] (the forward initialises it: the checkpoint may be
+ * uninitialised memory).  The layout is the library's; the same B must be passed to the backward */
 size_t ud_mpm_ckpt_bytes(const ud_mpm* h, int B);
 /* Which kernels a call with B envs runs (the choice is the library's, by measurement: DESIGN.md 3.2); for logs and benchmark
  * labels, nothing at this boundary depends on it.  0: one workgroup per env (bodies up to 128 particles, one box primitive).
@@ -259,7 +262,8 @@ int ud_mpm_reset(ud_mpm* h, void* stream);
  * it when it next synchronises: 0 ok.  One-workgroup path: 1 = LDS cell table overflow in that env (outputs invalid).
  * Many-workgroup path, a bit mask: 1 = the grid checkpoint of that env is incomplete -- its pool ran out, or (persistent forward) a
  * part of 32 particles touched more cells than its 512-slot table holds and sent the rest to the HBM grid directly (outputs valid; that
- * step's backward must recompute the grid: clip bit 1 of ud_mpm_step_bwd); 2 = a part's spill list overflowed as well (more than 896
+ * step's backward must recompute the grid for that env: clip bit 2 of ud_mpm_step_bwd lets the backward see the same fact in the
+ * checkpoint and decide per env on the device; clip bit 1 forces it for every env); 2 = a part's spill list overflowed as well (more than 896
  * cells for 32 particles: cannot happen with a 27-cell stencil; outputs invalid); 4 = a workgroup gave up waiting for a sibling
  * (outputs invalid; call ud_mpm_reset before the next step). */
 int ud_mpm_step_fwd(ud_mpm* h, int B, const float* x, const float* v, const float* C, const float* F, const float* J,
@@ -280,7 +284,14 @@ int ud_mpm_step_fwd(ud_mpm* h, int B, const float* x, const float* v, const floa
  * clip bit 0 applies norm_grad_state / norm_grad (nan_to_num + global-norm clip to 1, :389-408); in soft-contact
  * mode the norm also covers the cotangents of the primitive's rotation, size, friction and action_scale leaves.
  * clip bit 1 (many-workgroup path with grid_ckpt_cells > 0): ignore the grid checkpoint and recompute p2g + grid op --
- * for a step whose forward flagged a pool overflow in status[]; the particle history in the checkpoint is always complete. */
+ * for a step whose forward flagged a pool overflow in status[]; the particle history in the checkpoint is always complete.
+ * clip bit 2 (value 4; same handles): decide per env, on the device, from the word the forward left in the checkpoint -- every env whose
+ * word is clear restores its grid from the checkpoint, every env whose word is set recomputes p2g + grid op, in this same call.  The
+ * host reads nothing: a forward / backward pair needs no host code between its two calls (clip = 1 | 4 is the whole binding, under
+ * jit or inside a captured graph too).  Bit 1 wins over bit 2 (every env recomputes).  Bit 2 is ignored where there is no grid
+ * checkpoint to choose from: the one-workgroup path, grid_ckpt_cells = 0, deterministic mode.
+ * status [B] int32 of the backward: 0 ok; deterministic mode: 1 = more than 32768 touched cells in that env; under clip bit 2, value 8 =
+ * the grid of that env was recomputed (a report, not an error). */
 int ud_mpm_step_bwd(ud_mpm* h, int B, const void* ckpt, const float* prim_size, const float* friction,
                     const float* mu, const float* lamda, const float* action, const float* g_x, const float* g_v,
                     const float* g_C, const float* g_F, const float* g_prim_position, const float* g_prim_rotation, int clip,

@@ -259,8 +259,9 @@ class APG:
             raise RuntimeError("APG.capture: run the learner under a non-default stream (with torch.cuda.stream(s): ...), eager updates included")
         # The many-workgroup MPM path with a grid checkpoint hands a per-step overflow flag from the forward to the backward THROUGH THE
         # HOST (SimpleMPMSimulator._stage_flags: a side stream, pinned memory, an event the backward synchronises on): none of that can be
-        # recorded into a graph -- the capture would fail, or bake in the flag of the capturing run.
-        if sim is not None and getattr(sim, "_h_large", False) and getattr(sim, "grid_ckpt_cells", 0) > 0:
+        # recorded into a graph -- the capture would fail, or bake in the flag of the capturing run.  With device_handoff the flag stays
+        # on the device (inside the checkpoint; the backward chooses per env) and the update captures like any other.
+        if sim is not None and getattr(sim, "_h_large", False) and getattr(sim, "grid_ckpt_cells", 0) > 0 and not getattr(sim, "device_handoff", False):
             raise RuntimeError("APG.capture: this env's simulator stages grid-checkpoint flags through the host per step "
                                "(many-workgroup MPM path with grid_ckpt_cells > 0); run it eagerly")
         # the warm-up updates below are real updates (with zero noise): parameters and Adam moments are put back afterwards, IN PLACE --

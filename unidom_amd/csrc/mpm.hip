@@ -1391,7 +1391,7 @@ int ud_mpm_step_bwd(ud_mpm* h, int B, const void* ckpt, const float* prim_size, 
   ud::MpmBwdArgs a{};
   a.c = h->c; a.material = h->d_material; a.hard = h->d_hard; a.B = B; a.ckpt = (const float*)ckpt;
   a.psize = prim_size; a.friction = friction; a.mu = mu; a.lamda = lamda; a.action = action;
-  a.gx = g_x; a.gv = g_v; a.gC = g_C; a.gF = g_F; a.gppos = g_prim_position; a.clip = clip;
+  a.gx = g_x; a.gv = g_v; a.gC = g_C; a.gF = g_F; a.gppos = g_prim_position; a.clip = clip & ~4;   // bit 2: nothing to choose from on this path
   a.gx0 = g_x0; a.gv0 = g_v0; a.gC0 = g_C0; a.gF0 = g_F0; a.gppos0 = g_prim_position0; a.gfric = g_friction;
   a.gmu = g_mu; a.glam = g_lamda; a.gaction = g_action; a.status = status;
   if (h->nthreads_bwd_ws > 0)

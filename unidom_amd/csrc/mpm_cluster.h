@@ -291,6 +291,7 @@ __global__ void __launch_bounds__(64) lg_fk_all(LargeArgs a) {
     if (tid < 51) a.w.count[(tid - 48) * a.B + b] = 0;
     else if (a.gck_base) gck_idx(a, b)[0] = 0;
   }
+  if (ip == 0 && tid == 52 && a.gck_base) *gck_flag(a, b) = 0;   // both forwards: the checkpoint is the caller's uninitialised memory
   const long bp = (long)b * a.c.n_prim + ip;
   float* pp = a.w.ppos + bp * S * 3;
   float* pr = a.w.prot + bp * S * 4;
@@ -530,8 +531,8 @@ __global__ void __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(2))) clm
           float4* r = rpool + (long)(ob + j) * 2;
           r[0] = make_float4(__builtin_bit_cast(float, klist[e]), mv.x, mv.y, mv.z);
           r[1] = make_float4(mv.w, vv.x, vv.y, vv.z);
-        } else if (a.status) {
-          atomicOr(&a.status[b], 1);     // pool exhausted: the backward of this env recomputes the grid (clip bit 1), as on the multi-kernel path
+        } else {
+          s_spilled = 1;                 // pool exhausted: the grid checkpoint of this env is incomplete, reported with the spills below
         }
       }
       __syncthreads();  // vel / raw (= val), key and the cell list of substep f - 1 are rewritten by the next substep
@@ -560,7 +561,10 @@ __global__ void __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(2))) clm
   }
   // status: 1 = cells went past a part's table, so the grid checkpoint of this env is incomplete (outputs valid; the backward recomputes the
   // grid: clip bit 1); 2 = a part's spill list overflowed too, 4 = a part gave up waiting for its siblings (outputs invalid either way)
-  if (tid == 0 && a.status && recs && s_spilled) atomicOr(&a.status[b], 1);
+  if (tid == 0 && recs && s_spilled) {
+    atomicOr(ridx + gck_flag_slot(S), 1);   // = gck_flag(a, b): what the backward of this step reads on the device (clip bit 2)
+    if (a.status) atomicOr(&a.status[b], 1);
+  }
   if (tid == 0 && a.status && (s_ovf || s_dead)) atomicOr(&a.status[b], s_dead ? 4 : 2);
 }
 

@@ -86,6 +86,10 @@ struct LargeArgs {
   const float *psize, *friction, *mu, *lamda, *action;
   // logical launch shape of the per-substep kernels: (nbx blocks per env) x (Bg envs), issued as a ONE-dimensional grid (lg_bid)
   int nbx, Bg, xcd;
+  // env selector of the backward under clip bit 2 (lg_bid): 0 = every env; 1 = only the envs whose checkpoint word (gck_flag, written by
+  // the forward beside gck_idx) is clear -- they restore the grid; 2 = only those whose word is set -- they recompute it
+  int sel;
+  const int* sel_flag;    // env 0's word (env stride hist_stride_b floats); read only where sel != 0
   // deterministic backward (ud_mpm_conf.deterministic, position control; null otherwise): every sum that an atomic would order by arrival goes
   // to an array instead and is added up in a fixed order by a kernel of its own (mpm_det.hip)
   float* det_cellred;     // [B][det_capc][det_K] per listed cell (the list is sorted): what the grid-op adjoint adds to the env's cotangents --
@@ -114,7 +118,7 @@ __device__ __forceinline__ LgB lg_bid(const LargeArgs& a) {
     o.y = id / a.nbx;
     o.x = id % a.nbx;
   }
-  o.ok = o.y < a.Bg;
+  o.ok = o.y < a.Bg && (a.sel == 0 || (a.sel_flag[(long)(o.y + a.b0) * a.hist_stride_b] != 0) == (a.sel == 2));   // the DECODED env: xcd interleaves them
   return o;
 }
 
@@ -143,6 +147,9 @@ __device__ __forceinline__ int lg_bslot(const LargeArgs& a, int f) { return a.gp
 __device__ __forceinline__ int user_index(const LargeArgs& a, int b, int p) { return a.perm ? a.perm[(long)b * a.perm_stride + p] : p; }
 
 __device__ __forceinline__ int* gck_idx(const LargeArgs& a, int b) { return (int*)(a.gck_base + (long)b * a.hist_stride_b + a.gck_off_idx); }
+// one word behind the record index [S + 1]: != 0 = this env's grid checkpoint is incomplete (the forward raised status bit 0)
+__host__ __device__ constexpr long gck_flag_slot(int S) { return (long)S + 1; }
+__device__ __forceinline__ int* gck_flag(const LargeArgs& a, int b) { return gck_idx(a, b) + gck_flag_slot(a.c.steps); }
 __device__ __forceinline__ float4* gck_pool(const LargeArgs& a, int b) { return (float4*)(a.gck_base + (long)b * a.hist_stride_b + a.gck_off_pool); }
 __device__ __forceinline__ float4* gck_crec(const LargeArgs& a, int b) { return (float4*)(a.gck_base + (long)b * a.hist_stride_b + a.gck_off_crec); }
 
@@ -366,6 +373,7 @@ __global__ void __launch_bounds__(256) lg_clear_fk(LargeArgs a, int do_fk, int c
       int* idx = gck_idx(a, b);
       idx[f] = (f == 0) ? 0 : idx[f - 1] + n;
     }
+    if (tid == 0 && clear_bwd && a.status && f == S - 1) atomicOr(&a.status[b], 8);   // backward under clip bit 2 (a.status set): this env's grid is recomputed
     if (do_fk)
     for (int ip = 0; ip < a.c.n_prim; ++ip) {
       const long bp = (long)b * a.c.n_prim + ip;
@@ -697,6 +705,9 @@ __global__ void __launch_bounds__(256) lg_grid(LargeArgs a, int to_vel) {
     if (lgb_.x == 0 && threadIdx.x == 0) {
       a.w.count[a.lnext * a.B + b] = 0;                              // the list the next substep's p2g fills (nobody reads it in this launch)
       if (a.gck_base && a.f < a.c.steps) gck_idx(a, b)[a.f + 1] = gck_idx(a, b)[a.f] + n;   // records of substep f + 1 start where these end
+      // the launch after the last substep: a record fell outside the pool (lg_grid_cell raised status bit 0) exactly when the index ran
+      // past the budget -- the word this step's backward reads on the device (clip bit 2)
+      else if (a.gck_base) *gck_flag(a, b) = gck_idx(a, b)[a.c.steps] > a.gck_budget;
     }
     n = max(n, min(a.w.count[a.lprev * a.B + b], a.cap));
     if (a.f >= a.c.steps) {                                           // the launch after the last substep: only the retiring
@@ -2362,7 +2373,7 @@ static CkLayout ck_layout(const MpmLarge* L, int B) {
   k.off_tail = (S + 1) * k.rec;
   k.off_idx = k.off_tail + (long)c.n_prim * S * 10;
   k.off_idx = (k.off_idx + 3) / 4 * 4;                         // float4 alignment of the pool behind it
-  const long nidx = c.gck > 0 ? (S + 1 + 3) / 4 * 4 : 0;
+  const long nidx = c.gck > 0 ? (gck_flag_slot((int)S) + 1 + 3) / 4 * 4 : 0;       // [S + 1] first records, then the env's "checkpoint incomplete" word (gck_flag)
   k.off_pool = k.off_idx + nidx;
   const long budget = c.gck > 0 ? S * (long)c.gck * c.N : 0;   // records per env and launch: gck cells per particle and substep on average
   k.budget = (int)std::min<long>(budget, 0x7fffffff / 2);
@@ -2414,6 +2425,7 @@ static LargeArgs base_args(MpmLarge* L, int B, const float* psize, const float* 
   a.hist_in = nullptr; a.hist_out = nullptr; a.hist_stride_b = 0; a.b0 = 0;
   a.gck_base = nullptr; a.gck_off_idx = 0; a.gck_off_pool = 0; a.gck_budget = 0; a.status = nullptr; a.gpar = 0;
   a.svd_rows = 0; a.ls3 = 0; a.vb = 0; a.ls = 0; a.lprev = 0; a.lnext = 0; a.nbx = 1; a.Bg = 0; a.xcd = 0;
+  a.sel = 0; a.sel_flag = nullptr;
   a.perm = nullptr; a.perm_stride = 0;
   a.det_cellred = nullptr; a.det_capc = 0; a.det_K = 0; a.det_pacc = nullptr; a.det_normpart = nullptr;
   a.psize = psize; a.friction = friction; a.mu = mu; a.lamda = lamda; a.action = action;
@@ -2687,82 +2699,11 @@ int mpm_large_step_fwd(MpmLarge* L, int B, const float* x, const float* v, const
   return UD_OK;
 }
 
-int mpm_large_step_bwd(MpmLarge* L, int B, const float* ckpt, const float* psize, const float* friction, const float* mu,
-                       const float* lamda, const float* action, const float* gx, const float* gv, const float* gC, const float* gF,
-                       const float* gppos, const float* gprot, int clip, float* gx0, float* gv0, float* gC0, float* gF0, float* gppos0,
-                       float* grot0, float* gfric, float* gmu, float* glam, float* gaction, int* status, hipStream_t st) {
-  if (B > L->B) { set_error("ud_mpm_step_bwd: B=%d exceeds the handle's max_envs=%d", B, L->B); return UD_ERR_INVALID; }
+// the reverse substeps of the envs `a.sel` selects: restoring the grid (two launches per substep where `fused`, else four) or recomputing it
+static void lg_bwd_substeps(MpmLarge* L, LargeArgs a, const float* ckpt, long rec, int lanes, bool gck, bool fused, int G, const LgGroup* grp) {
   const MpmConst& c = L->c;
-  const int S = c.steps, N = c.N, Np = c.Np;
+  const int S = c.steps, N = c.N;
   const dim3 blk(256), blks(LG_SCATTER_T);
-  const int lanes = lg_lanes(L, B);                      // lanes per particle in the four particle kernels
-  LargeArgs a = base_args(L, B, psize, friction, mu, lamda, action);
-  const CkLayout ck = ck_layout(L, B);
-  const long rec = ck.rec;
-  const long stride_b = ck.stride;
-  a.hist_stride_b = stride_b;
-  a.svd_rows = lg_svd_rows(L, B) ? 1 : 0;                 // the forward's SVD factors ride in the records: read, not iterated again
-  // restore the grid from the checkpoint instead of recomputing p2g + grid op -- unless the caller saw the forward flag a
-  // pool overflow and asks for the recomputing backward (clip bit 1)
-  const bool gck = ck.budget > 0 && !(clip & 2);
-  clip &= 1;
-  if (gck) { a.gck_base = const_cast<float*>(ckpt); a.gck_off_idx = ck.off_idx; a.gck_off_pool = ck.off_pool; a.gck_budget = ck.budget; }
-  if (gck && lg_crec(L, B)) a.gck_off_crec = ck.off_crec;
-  if (c.sort && N <= LG_SORT_MAX) { a.perm = (const int*)(ckpt + ck.off_perm); a.perm_stride = stride_b; }   // the forward's order
-  if (status) (void)hipMemsetAsync(status, 0, (size_t)B * sizeof(int), st);
-  // The backward is the multi-kernel path, restoring the grid from the checkpoint that either forward wrote.  (A persistent cluster
-  // backward -- recomputing the grid, or restoring it from per-part records -- was built in round 3 and measured no faster: 256 VGPRs +
-  // scratch at two waves per SIMD, and its long chains are single-wave latency either way; a three-launch form where the two-launch one
-  // does not apply was measured slower.  Both are gone: git history, DESIGN.md 3.2.)
-  // Two launches per reverse substep (lg_gadj_restore, lg_padj_gadj) where the backward restores the grid, four lanes work on a
-  // particle and one primitive touches the grid.  Measured on 1x MI355X, 32 envs, backward ms per step, four-kernel / two-launch
-  // (profiles/r03c_fused_bwd_groups.txt): rope at n_grid 128 (position control) 2.88 / 2.45 in one env group, 2.76 / 2.92 in two;
-  // shape_rope (soft contact: the grid-op adjoint is the long launch and overlaps the other groups' particle launches)
-  // 6.08 / 6.00 in one, 5.98 / 5.65 in two, 7.24 / 5.25 in four; pour_water (two container primitives) 1.35 / 1.61: kept on four.
-  const bool fused = gck && lg_two_launch_bwd(L, lanes);
-  LgGroup grp[MpmLarge::MAX_GROUPS];
-  const int G = lg_fork(L, B, st, grp, fused ? (c.position_control ? 1 : 4) : 0);
-  for (int g = 0; g < G; ++g) {
-    a.b0 = grp[g].b0;
-    hipLaunchKernelGGL(lg_bwd_in, dim3(grp[g].Bg, c.n_prim), blk, 0, grp[g].s, a, ckpt + ck.off_tail, stride_b, gppos, gprot);
-    hipLaunchKernelGGL(lg_pack, dim3((N + 255) / 256, grp[g].Bg), blk, 0, grp[g].s, c, a.b0, gx, gv, gC, gF, L->w.gstate, (long)24 * Np, 0, a.perm, a.perm_stride);
-  }
-  if (c.det) {
-    // Deterministic backward: the recomputing backward with every arrival-ordered sum replaced -- the grid of substep f comes
-    // from the deterministic forward's own kernels (ordered (m, mv) sums), the g2p adjoint's scatter is an ordered sum per cell over (offset,
-    // particle) (lg_g2p_adj_det -> det_cells_kernel<1>), the per-env cotangents of the grid-op adjoint, the mu / lamda cotangents and the clip's
-    // norm are added up in a fixed order.  One lane per particle, one stream.  Two calls on the same inputs return the same bits.
-    DetArgs d = lg_det_args(L, B, psize, friction, mu, lamda, action);
-    d.hist = const_cast<float*>(ckpt); d.rec = rec; d.stride_b = stride_b; d.pingpong = 0; d.bwd = 1;
-    d.val_out = (float*)L->w.val; d.gacc = (float*)L->w.gacc; d.acc = L->w.acc; d.gpv = L->w.gpv; d.status = status;
-    char* db = (char*)L->det_arena;
-    a.det_cellred = d.cellred; a.det_capc = d.capc; a.det_K = d.K; a.det_pacc = (float*)(db + L->det_off[12]); a.det_normpart = (float*)(db + L->det_off[13]);
-    a.b0 = 0; a.gck_base = nullptr; a.svd_rows = 0; a.perm = nullptr;
-    const dim3 gc(lg_cell_blocks(L->cap), B), gq((N + 255) / 256, B), gqf(gq.x + c.n_prim, B);
-    int rc = UD_OK;
-    for (int f = S - 1; f >= 0 && rc == UD_OK; --f) {
-      a.f = f; a.hist_in = ckpt + (long)f * rec;
-      d.keylist = L->w.list + (long)(f & 1) * L->B * L->cap; d.keycount = L->w.count + (long)(f & 1) * L->B;
-      rc = mpm_det_bwd_recompute(d, f, &L->det_epoch, st);
-      {
-        hipStream_t s = st;
-        LG_LAUNCH(lg_g2p_adj_det, gq.x, (int)gq.y, blk, 0, s, (float4*)d.contrib);
-        if (rc == UD_OK) rc = mpm_det_bwd_gcells(d, f, L->det_epoch, st);
-        LG_LAUNCH(lg_grid_adj_det, gc.x, (int)gc.y, blk, 0, s);
-        if (rc == UD_OK) rc = mpm_det_bwd_reduce_cells(d, f, st);
-        LG_LAUNCH(lg_p2g_adj<1>, gqf.x, (int)gqf.y, blk, 0, s, (int)gq.x);
-        if (rc == UD_OK) rc = mpm_det_bwd_clear(d, st);
-      }
-    }
-    if (rc == UD_OK) rc = mpm_det_bwd_reduce_particles(d, st);
-    a.f = -1;
-    const dim3 gp((N + 255) / 256, B);
-    if (clip) hipLaunchKernelGGL(lg_bwd_norm, gp, blk, 0, st, a);
-    hipLaunchKernelGGL(lg_bwd_out, gp, blk, 0, st, a, clip, gx0, gv0, gC0, gF0, gppos0, gfric, gmu, glam, gaction, grot0);
-    const hipError_t e = hipGetLastError();
-    if (rc != UD_OK || e != hipSuccess) { set_error("ud_mpm_step_bwd (deterministic): %s", rc != UD_OK ? "launch failed" : hipGetErrorString(e)); return rc != UD_OK ? rc : UD_ERR_HIP; }
-    return UD_OK;
-  }
   if (fused) {
     a.gpar = 1;
     for (int g = 0; g < G; ++g) {
@@ -2811,6 +2752,107 @@ int mpm_large_step_bwd(MpmLarge* L, int B, const float* ckpt, const float* psize
       const dim3 gqf(gq.x + c.n_prim, Bg);   // + one block per primitive: the FK adjoint
       if (lanes == 4) LG_LAUNCH(lg_p2g_adj<4>, gqf.x, (int)gqf.y, blk, 0, s, (int)gq.x); else LG_LAUNCH(lg_p2g_adj<1>, gqf.x, (int)gqf.y, blk, 0, s, (int)gq.x);
     }
+  }
+}
+
+int mpm_large_step_bwd(MpmLarge* L, int B, const float* ckpt, const float* psize, const float* friction, const float* mu,
+                       const float* lamda, const float* action, const float* gx, const float* gv, const float* gC, const float* gF,
+                       const float* gppos, const float* gprot, int clip, float* gx0, float* gv0, float* gC0, float* gF0, float* gppos0,
+                       float* grot0, float* gfric, float* gmu, float* glam, float* gaction, int* status, hipStream_t st) {
+  if (B > L->B) { set_error("ud_mpm_step_bwd: B=%d exceeds the handle's max_envs=%d", B, L->B); return UD_ERR_INVALID; }
+  const MpmConst& c = L->c;
+  const int S = c.steps, N = c.N, Np = c.Np;
+  const dim3 blk(256);
+  const int lanes = lg_lanes(L, B);                      // lanes per particle in the four particle kernels
+  LargeArgs a = base_args(L, B, psize, friction, mu, lamda, action);
+  const CkLayout ck = ck_layout(L, B);
+  const long rec = ck.rec;
+  const long stride_b = ck.stride;
+  a.hist_stride_b = stride_b;
+  a.svd_rows = lg_svd_rows(L, B) ? 1 : 0;                 // the forward's SVD factors ride in the records: read, not iterated again
+  // restore the grid from the checkpoint instead of recomputing p2g + grid op -- unless the caller saw the forward flag a
+  // pool overflow and asks for the recomputing backward (clip bit 1)
+  const bool gck = ck.budget > 0 && !(clip & 2);
+  // clip bit 2: restore or recompute per env, decided on the device from the word the forward left in the checkpoint (gck_flag) -- two
+  // passes over disjoint sets of envs (LargeArgs::sel).  Bit 1 wins; without a grid checkpoint to choose from the bit means nothing.
+  const bool per_env = (clip & 4) && gck && !c.det;
+  const bool report_all = (clip & 4) && (clip & 2) && ck.budget > 0 && !c.det;   // bit 1 won: every env recomputes, and says so (8)
+  clip &= 1;
+  if (gck) { a.gck_base = const_cast<float*>(ckpt); a.gck_off_idx = ck.off_idx; a.gck_off_pool = ck.off_pool; a.gck_budget = ck.budget; }
+  if (gck && lg_crec(L, B)) a.gck_off_crec = ck.off_crec;
+  if (c.sort && N <= LG_SORT_MAX) { a.perm = (const int*)(ckpt + ck.off_perm); a.perm_stride = stride_b; }   // the forward's order
+  if (status) (void)hipMemsetAsync(status, 0, (size_t)B * sizeof(int), st);
+  // The backward is the multi-kernel path, restoring the grid from the checkpoint that either forward wrote.  (A persistent cluster
+  // backward -- recomputing the grid, or restoring it from per-part records -- was built in round 3 and measured no faster: 256 VGPRs +
+  // scratch at two waves per SIMD, and its long chains are single-wave latency either way; a three-launch form where the two-launch one
+  // does not apply was measured slower.  Both are gone: git history, DESIGN.md 3.2.)
+  // Two launches per reverse substep (lg_gadj_restore, lg_padj_gadj) where the backward restores the grid, four lanes work on a
+  // particle and one primitive touches the grid.  Measured on 1x MI355X, 32 envs, backward ms per step, four-kernel / two-launch
+  // (profiles/r03c_fused_bwd_groups.txt): rope at n_grid 128 (position control) 2.88 / 2.45 in one env group, 2.76 / 2.92 in two;
+  // shape_rope (soft contact: the grid-op adjoint is the long launch and overlaps the other groups' particle launches)
+  // 6.08 / 6.00 in one, 5.98 / 5.65 in two, 7.24 / 5.25 in four; pour_water (two container primitives) 1.35 / 1.61: kept on four.
+  const bool fused = gck && lg_two_launch_bwd(L, lanes);
+  LgGroup grp[MpmLarge::MAX_GROUPS];
+  int G = lg_fork(L, B, st, grp, fused ? (c.position_control ? 1 : 4) : 0);
+  for (int g = 0; g < G; ++g) {
+    a.b0 = grp[g].b0;
+    hipLaunchKernelGGL(lg_bwd_in, dim3(grp[g].Bg, c.n_prim), blk, 0, grp[g].s, a, ckpt + ck.off_tail, stride_b, gppos, gprot);
+    hipLaunchKernelGGL(lg_pack, dim3((N + 255) / 256, grp[g].Bg), blk, 0, grp[g].s, c, a.b0, gx, gv, gC, gF, L->w.gstate, (long)24 * Np, 0, a.perm, a.perm_stride);
+  }
+  if (c.det) {
+    // Deterministic backward: the recomputing backward with every arrival-ordered sum replaced -- the grid of substep f comes
+    // from the deterministic forward's own kernels (ordered (m, mv) sums), the g2p adjoint's scatter is an ordered sum per cell over (offset,
+    // particle) (lg_g2p_adj_det -> det_cells_kernel<1>), the per-env cotangents of the grid-op adjoint, the mu / lamda cotangents and the clip's
+    // norm are added up in a fixed order.  One lane per particle, one stream.  Two calls on the same inputs return the same bits.
+    DetArgs d = lg_det_args(L, B, psize, friction, mu, lamda, action);
+    d.hist = const_cast<float*>(ckpt); d.rec = rec; d.stride_b = stride_b; d.pingpong = 0; d.bwd = 1;
+    d.val_out = (float*)L->w.val; d.gacc = (float*)L->w.gacc; d.acc = L->w.acc; d.gpv = L->w.gpv; d.status = status;
+    char* db = (char*)L->det_arena;
+    a.det_cellred = d.cellred; a.det_capc = d.capc; a.det_K = d.K; a.det_pacc = (float*)(db + L->det_off[12]); a.det_normpart = (float*)(db + L->det_off[13]);
+    a.b0 = 0; a.gck_base = nullptr; a.svd_rows = 0; a.perm = nullptr;
+    const dim3 gc(lg_cell_blocks(L->cap), B), gq((N + 255) / 256, B), gqf(gq.x + c.n_prim, B);
+    int rc = UD_OK;
+    for (int f = S - 1; f >= 0 && rc == UD_OK; --f) {
+      a.f = f; a.hist_in = ckpt + (long)f * rec;
+      d.keylist = L->w.list + (long)(f & 1) * L->B * L->cap; d.keycount = L->w.count + (long)(f & 1) * L->B;
+      rc = mpm_det_bwd_recompute(d, f, &L->det_epoch, st);
+      {
+        hipStream_t s = st;
+        LG_LAUNCH(lg_g2p_adj_det, gq.x, (int)gq.y, blk, 0, s, (float4*)d.contrib);
+        if (rc == UD_OK) rc = mpm_det_bwd_gcells(d, f, L->det_epoch, st);
+        LG_LAUNCH(lg_grid_adj_det, gc.x, (int)gc.y, blk, 0, s);
+        if (rc == UD_OK) rc = mpm_det_bwd_reduce_cells(d, f, st);
+        LG_LAUNCH(lg_p2g_adj<1>, gqf.x, (int)gqf.y, blk, 0, s, (int)gq.x);
+        if (rc == UD_OK) rc = mpm_det_bwd_clear(d, st);
+      }
+    }
+    if (rc == UD_OK) rc = mpm_det_bwd_reduce_particles(d, st);
+    a.f = -1;
+    const dim3 gp((N + 255) / 256, B);
+    if (clip) hipLaunchKernelGGL(lg_bwd_norm, gp, blk, 0, st, a);
+    hipLaunchKernelGGL(lg_bwd_out, gp, blk, 0, st, a, clip, gx0, gv0, gC0, gF0, gppos0, gfric, gmu, glam, gaction, grot0);
+    const hipError_t e = hipGetLastError();
+    if (rc != UD_OK || e != hipSuccess) { set_error("ud_mpm_step_bwd (deterministic): %s", rc != UD_OK ? "launch failed" : hipGetErrorString(e)); return rc != UD_OK ? rc : UD_ERR_HIP; }
+    return UD_OK;
+  }
+  if (!per_env) {
+    if (report_all) a.status = status;
+    lg_bwd_substeps(L, a, ckpt, rec, lanes, gck, fused, G, grp);
+    a.status = nullptr;
+  } else {
+    // Each env takes exactly one of the two sequences; they share no per-env state (grids, lists, counts, cotangents and sums are all
+    // indexed by env) and each leaves its own envs' grids all-zero.  The prologue above and the epilogue below run once, for every
+    // env: the join and the second fork order them against both passes, whichever groups an env falls into.
+    a.sel_flag = (const int*)(ckpt + ck.off_idx) + gck_flag_slot(S);
+    a.sel = 1;
+    lg_bwd_substeps(L, a, ckpt, rec, lanes, true, fused, G, grp);
+    lg_join(L, G, st, grp);
+    G = lg_fork(L, B, st, grp);
+    LargeArgs r = a;
+    r.sel = 2; r.status = status;                         // lg_clear_fk reports 8 for the envs this pass takes
+    r.gck_base = nullptr; r.gck_off_idx = 0; r.gck_off_pool = 0; r.gck_off_crec = 0; r.gck_budget = 0;
+    lg_bwd_substeps(L, r, ckpt, rec, lanes, false, false, G, grp);
+    a.sel = 0;
   }
   a.f = -1;
   for (int g = 0; g < G; ++g) {

@@ -70,8 +70,14 @@ class _Step(torch.autograd.Function):
             *[_lib.ptr(t) for t in (xo, vo, Co, Fo, Jo, ppo, pro, pvo, pwo)], _lib.ptr(ckpt), _lib.ptr(status), stream),
             "ud_mpm_step_fwd")
         sim._prof_end(ev)
-        ctx.overflow = None
-        if ckpt is not None and sim.grid_ckpt_cells > 0 and sim._h_large:
+        ctx.overflow, ctx.handoff = None, False
+        if ckpt is not None and sim.grid_ckpt_cells > 0 and sim._h_large and sim._handoff():
+            # device_handoff: the same flag sits in the checkpoint, where this step's backward reads it per env (clip bit 2).  No side
+            # stream, no pinned buffer, no event; bit 0 is not an error, the error bits (2, 4) go the way of every other status word.
+            ctx.handoff = True
+            sim.last_status["fwd"] = status
+            sim.status_log.append(status & 6)
+        elif ckpt is not None and sim.grid_ckpt_cells > 0 and sim._h_large:
             # the only flag this path raises is "grid-checkpoint pool exhausted": not an error -- that step's backward recomputes
             # the grid instead.  The flags travel to pinned host memory on a side stream, so the backward reads them without a sync.
             ctx.overflow = sim._stage_flags(status)
@@ -105,11 +111,16 @@ class _Step(torch.autograd.Function):
         status = torch.empty((B,), dtype=torch.int32, device=dev)   # every entry is written by the call (include/unidom_hip.h)
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         ev = sim._prof_begin("bwd")
+        clip = (1 if sim.clip_grad else 0) | (4 if ctx.handoff else (2 if sim._overflowed(ctx.overflow) else 0))
         _lib.check(L.ud_mpm_step_bwd(
             sim._h, C.c_int(B), _lib.ptr(ckpt), *[_lib.ptr(t) for t in (psize, friction, mu, lamda, action)],
-            *[_lib.ptr(t) for t in (gx, gv, gC, gF, gppos, gprot)], C.c_int((1 if sim.clip_grad else 0) | (2 if sim._overflowed(ctx.overflow) else 0)),
+            *[_lib.ptr(t) for t in (gx, gv, gC, gF, gppos, gprot)], C.c_int(clip),
             *[_lib.ptr(t) for t in (ox, ov, oC, oF, opp, opr, ofr, omu, ola, oa)], _lib.ptr(status), stream), "ud_mpm_step_bwd")
         sim._prof_end(ev)
+        if ctx.handoff:                        # value 8 = "this env's grid was recomputed": counted on the device, not an error
+            sim.last_status["bwd"] = status
+            sim._recomputed.add_((status & 8).ne(0).sum())
+            status = status & ~8
         sim.status_log.append(status)
         fs, ms, ls = ctx.pshape
         return (None, ox, ov, oC, oF, None, opp, opr, None, ofr.reshape(fs), omu.reshape(ms), ola.reshape(ls), oa)
@@ -120,6 +131,12 @@ class SimpleMPMSimulator:
     # bwd_two_launch, collide_records; include/unidom_hip.h).  Empty = the library's choice by measurement.  Copied into `self.tuning` when a simulator
     # is built and fixed for a handle when it is created (_make_handle) -- there is no per-call switch; diagnostics and the tests set it.
     default_tuning: dict = {}
+    # Many-workgroup path with grid_ckpt_cells > 0: how "this env's grid-checkpoint pool ran out" travels from a step's forward to its
+    # backward.  False: through the host (_stage_flags / _overflowed: side stream, pinned memory, an event the backward waits on; one
+    # flagged env makes the whole batch recompute).  True: inside the checkpoint -- the backward (clip bit 2, include/unidom_hip.h)
+    # restores or recomputes per env on the device, no host code between the two calls, so an update can be captured as one graph.
+    # Also read from conf.device_handoff; fixed before the first step.
+    device_handoff: bool = False
 
     def __init__(self, conf, batch_size, use_position_control=False, device="cuda"):
         self.conf = conf
@@ -156,7 +173,11 @@ class SimpleMPMSimulator:
         self._h = None
         self._h_large = False            # the handle runs the many-workgroup path (N > 128 or soft contact)
         self._flag_stream = None
-        self.grid_ckpt_overflows = 0     # steps whose backward fell back to recomputing the grid
+        self.grid_ckpt_overflows = 0     # steps whose backward fell back to recomputing the grid (host path)
+        self.device_handoff = bool(getattr(conf, "device_handoff", type(self).device_handoff))
+        self._handoff_fixed = None       # device_handoff as the first step found it
+        self._recomputed = None          # device_handoff: env-steps whose backward recomputed the grid (device scalar)
+        self.last_status = {}            # device_handoff: the raw status[] of the newest forward / backward ("fwd" / "bwd"; device tensors)
 
     # -- particle seeding (:65-145) ----------------------------------------------------------------------
     def add_box(self, conf, state, size, init_pos, hardness=1, z_rotation_angle=0, material=0, density=1):
@@ -291,6 +312,20 @@ class SimpleMPMSimulator:
         over = bool((host & 1).any())
         self.grid_ckpt_overflows += int(over)
         return over
+
+    def _handoff(self):
+        if self._handoff_fixed is None:
+            self._handoff_fixed = bool(self.device_handoff)
+            if self._handoff_fixed:
+                self._recomputed = torch.zeros((), dtype=torch.int64, device=self.device)
+        elif self._handoff_fixed != bool(self.device_handoff):
+            raise _lib.UnidomError("SimpleMPMSimulator.device_handoff is fixed before the first step")
+        return self._handoff_fixed
+
+    def grid_recomputed_env_steps(self):
+        """device_handoff: the number of env-steps so far whose backward recomputed the grid because the forward had flagged the env's
+        checkpoint incomplete (value 8 in the backward's status[]); 0 on the host path, whose counter is grid_ckpt_overflows.  Synchronises."""
+        return 0 if self._recomputed is None else int(self._recomputed.item())
 
     def _reset_after_failure(self, flags):
         """A part that gave up waiting (bit 4) skipped the zeroing of its cells: the handle's arenas go back to their rest state
