@@ -397,6 +397,7 @@ int ud_plb_loss_bwd(ud_plb* h, int B, const double* x, const double* prim_pos, c
  *                   idx_xy [B,P] / idx_yx [B,Q] (int32) are the argmins the backward routes the cotangent through.
  *   ud_cloth_pnp_*  core/envs/basic/cloth_env.py:134-173 get_pnp_actions (actions [B,6], primitive0 [B,4]) ->
  *                   macro_actions [40,B,8], and :206-209 contact_distance [B] = min_p |actions[:, :3] - x_p|.
+ *   ud_cloth_depth_* core/envs/basic/cloth_env.py:71-92 state_to_depth: the DEPTH observation (csrc/env_depth.hip), below.
  * P, Q <= 4096.  The backward entry points return what jax.grad returns for the same expressions.
  * ------------------------------------------------------------------------------------------------ */
 int ud_chamfer_fwd(int B, int P, int Q, const float* x, const float* y, float* out, int* idx_xy, int* idx_yx, void* stream);
@@ -408,6 +409,17 @@ int ud_cloth_pnp_fwd(int B, int P, const float* actions, const float* primitive0
 int ud_cloth_pnp_bwd(int B, int P, const float* actions, const float* x, const float* contact_distance,
                      const int* contact_idx, const float* g_macro_actions, const float* g_contact_distance,
                      float* g_actions, float* g_primitive0, float* g_x, void* stream);
+/* DEPTH observation, core/envs/basic/cloth_env.py:71-92 (state_to_depth), for each of M images (B envs, or T*B for a state list):
+ *   img [M,H,W] = zeros.at[py, px].set(x.y + z_offset) with px = clip(floor(x.x / pixel_size), 0, W-1), py = clip(floor(x.z /
+ *   pixel_size), 0, H-1).  The division is a true IEEE f32 division and the clip is taken on the float, so -inf / NaN land in
+ *   pixel 0 and +inf in the last one.  A pixel holds the height that is last in ascending (height, particle index) order
+ *   among the particles landing there (stable argsort, last write wins; NaN above +inf); untouched pixels are 0.
+ *   owner [M,P] (int32) = py*W + px for the particle that owns its pixel, -1 for every other; NULL when no backward follows.
+ *   ud_cloth_depth_bwd: g_x [M,P,3], written in full: g_x[p].y = g_img[owner[p]] for owners, every other entry 0.
+ * P <= 4096 and H*W <= 131072 (UD_ERR_UNSUPPORTED otherwise).  One launch each, bit-identical from run to run. */
+int ud_cloth_depth_fwd(int M, int P, int H, int W, float pixel_size, float z_offset, const float* x, float* img, int* owner,
+                       void* stream);
+int ud_cloth_depth_bwd(int M, int P, int H, int W, const int* owner, const float* g_img, float* g_x, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * MPM-env arithmetic either side of simulator.step (core/envs/basic/mpm_env.py), one workgroup per env.

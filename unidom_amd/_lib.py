@@ -20,7 +20,7 @@ SYMBOLS = [
     "ud_cloth_rollout_fwd", "ud_cloth_rollout_bwd",
     "ud_mpm_create", "ud_mpm_destroy", "ud_mpm_ckpt_bytes", "ud_mpm_ckpt_cells", "ud_mpm_launch_plan", "ud_mpm_reset", "ud_mpm_step_fwd", "ud_mpm_step_bwd",
     "ud_plb_create", "ud_plb_destroy", "ud_plb_launch_plan", "ud_plb_poll_timeouts", "ud_plb_step_fwd", "ud_plb_ckpt_bytes", "ud_plb_step_bwd", "ud_plb_loss_fwd", "ud_plb_loss_bwd",
-    "ud_chamfer_fwd", "ud_chamfer_bwd", "ud_cloth_pnp_fwd", "ud_cloth_pnp_bwd",
+    "ud_chamfer_fwd", "ud_chamfer_bwd", "ud_cloth_pnp_fwd", "ud_cloth_pnp_bwd", "ud_cloth_depth_fwd", "ud_cloth_depth_bwd",
     "ud_mpm_focus_fwd", "ud_mpm_focus_bwd", "ud_mpm_finish_fwd", "ud_mpm_finish_bwd",
 ]
 
@@ -86,6 +86,8 @@ def lib():
         for name in SYMBOLS:
             if not hasattr(L, name):
                 raise UnidomError(f"{SO_PATH} does not export {name}")
+        L.ud_cloth_depth_fwd.argtypes = [C.c_int] * 4 + [C.c_float] * 2 + [C.c_void_p] * 4
+        L.ud_cloth_depth_bwd.argtypes = [C.c_int] * 4 + [C.c_void_p] * 4
         _LIB = L
     return _LIB
 

@@ -1,4 +1,4 @@
-"""Fused device kernels for the cloth-env arithmetic around the rollout (libunidom_hip: csrc/env_glue.hip).
+"""Fused device kernels for the cloth-env arithmetic around the rollout (libunidom_hip: csrc/env_glue.hip, csrc/env_depth.hip).
 
 The reference jit-compiles step_diff, so XLA fuses calc_chamfer (core/utils/util.py:138-153), contact_distance
 (cloth_env.py:206-209) and get_pnp_actions (cloth_env.py:134-173) into a few kernels; op by op they are ~180 tiny
@@ -77,6 +77,43 @@ class PnpContactFn(torch.autograd.Function):
                                                _lib.ptr(g_macro), _lib.ptr(g_contact), _lib.ptr(ga), _lib.ptr(gp), _lib.ptr(gx),
                                                _stream(xc.device)), "ud_cloth_pnp_bwd")
         return ga, gp, gx
+
+
+class DepthFn(torch.autograd.Function):
+    """state_to_depth (cloth_env.py:71-92) of every image: x [M,P,3] -> img [M,H,W]; the cotangent of a pixel goes to the height of
+    the particle that owns it (heightmap.at[py, px].set(points[:, 1])), floor passes nothing to the x and z coordinates."""
+
+    H, W = 320, 320
+    PIXEL_SIZE, Z_OFFSET = 0.003125, 0.01
+
+    @staticmethod
+    def forward(ctx, x):
+        x = x.detach().to(torch.float32).contiguous()
+        M, P = x.shape[0], x.shape[1]
+        H, W = DepthFn.H, DepthFn.W
+        img = torch.empty((M, H, W), dtype=torch.float32, device=x.device)
+        owner = torch.empty((M, P), dtype=torch.int32, device=x.device) if ctx.needs_input_grad[0] else None
+        _lib.check(_lib.lib().ud_cloth_depth_fwd(M, P, H, W, DepthFn.PIXEL_SIZE, DepthFn.Z_OFFSET, _lib.ptr(x), _lib.ptr(img),
+                                                 _lib.ptr(owner), _stream(x.device)), "ud_cloth_depth_fwd")
+        ctx.save_for_backward(owner)
+        return img
+
+    @staticmethod
+    def backward(ctx, g):
+        owner, = ctx.saved_tensors
+        M, P = owner.shape
+        g = g.to(torch.float32).contiguous()
+        gx = torch.empty((M, P, 3), dtype=torch.float32, device=g.device)
+        _lib.check(_lib.lib().ud_cloth_depth_bwd(M, P, DepthFn.H, DepthFn.W, _lib.ptr(owner), _lib.ptr(g), _lib.ptr(gx),
+                                                 _stream(g.device)), "ud_cloth_depth_bwd")
+        return gx
+
+
+def depth(x):
+    """[..., P, 3] -> [..., 320, 320, 1]: the DEPTH observation of every leading index (B envs, or [T, B] for a state list)."""
+    lead = x.shape[:-2]
+    img = DepthFn.apply(x.reshape((-1,) + x.shape[-2:]))
+    return img.reshape(lead + (DepthFn.H, DepthFn.W, 1))
 
 
 def chamfer(x, goal):

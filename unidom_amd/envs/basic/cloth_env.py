@@ -3,6 +3,7 @@
 Mirrors /root/reference/DaXBench/daxbench/core/envs/basic/cloth_env.py (and cloth_env_para.py for the
 parameter-aware observation):
     __init__                :25-65      get_obs             :94-132   (para: cloth_env_para.py:101-137)
+    state_to_depth          :71-92      (the DEPTH observation; get_obs(obs_type=DEPTH) applies it to every env)
     get_pnp_actions         :134-173    build_reset/reset   :178-187
     step_diff               :201-231    get_collision_func  :239-243
 The reference jit-compiles step_diff around lax.scan(simulator.step_jax); here the scan is one kernel launch
@@ -72,8 +73,16 @@ class ClothEnv:
 
     # ------------------------------------------------------------------------------------------------
     def get_obs(self, state: ClothState, eval_min_max_stiff=None, obs_type=PARTICLE):
+        """PARTICLE: x | primitive0 | primitive1 (| normalised stiffness).  DEPTH: [..., 320, 320, 1], the top-down height map of
+        every env (and every substep of a state list), one kernel (csrc/env_depth.hip), differentiable in the heights.
+
+        The specification of DEPTH is state_to_depth (:71-92), the one variant of the reference's code that runs, applied to
+        every env: the same block inside the reference's get_obs (:99-117) sits under vmap and indexes points[0] of an
+        already unbatched array, so it cannot be evaluated.  RGB is pyrender's and stays out of scope."""
+        if obs_type == ClothEnv.DEPTH:
+            return _fused.depth(state.x)
         if obs_type != ClothEnv.PARTICLE:
-            raise NotImplementedError("only PARTICLE observations are on the hot path")
+            raise NotImplementedError("only PARTICLE and DEPTH observations are on the hot path")
         lead = state.x.shape[:-2]
         parts = [state.x.reshape(lead + (-1,)), state.primitive0, state.primitive1]
         mm = eval_min_max_stiff if eval_min_max_stiff is not None else self.eval_min_max_stiff
@@ -81,6 +90,11 @@ class ClothEnv:
             lo, hi = float(mm[0]), float(mm[1])
             parts.append((state.stiffness.to(torch.float32)[..., None] - lo) / (hi - lo))
         return torch.cat(parts, -1)
+
+    def state_to_depth(self, state: ClothState):
+        """[320,320,1] NumPy height map of env 0, as the reference's state_to_depth (:71-92) returns it."""
+        with torch.no_grad():
+            return _fused.depth(state.x[0]).cpu().numpy()
 
     @staticmethod
     def get_pnp_actions(actions, state: ClothState):
@@ -126,8 +140,9 @@ class ClothEnv:
             macro, contact_distance = _fused.pnp_and_contact(actions, state.primitive0, state.x)
             state, state_list = self.simulator.rollout(state, macro, want_lists=want_lists)          # :211
             state = state._replace(cur_step=state.cur_step + 1)                                      # :213
-            obs = self.get_obs(state)
-            obs_list = self.get_obs(state_list) if want_lists else obs                               # :216-219
+            obs_type = getattr(self.conf, "obs_type", ClothEnv.PARTICLE)   # opt-in: no shipped conf sets it
+            obs = self.get_obs(state, obs_type=obs_type)
+            obs_list = self.get_obs(state_list, obs_type=obs_type) if want_lists else obs            # :216-219
             done = state.cur_step >= self.max_steps
             chamfer_distance = _fused.chamfer(state.x, self.goal)                                    # :222
             reward = torch.exp(chamfer_distance * -10.0)                                             # :223  e ** (-10 d)

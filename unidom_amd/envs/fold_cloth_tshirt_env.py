@@ -39,8 +39,10 @@ class FoldTshirtEnv(ClothEnv):
         return mask.astype(np.float32)
 
     def get_obs(self, state, eval_min_max_stiff=None, obs_type=ClothEnv.PARTICLE):   # :69-111
+        """DEPTH is the base env's map (ClothEnv.get_obs).  The reference's own copy here (:78-94) is not the specification: it
+        discards the scatter's result and mixes 320 x 640 indices into a 320-row map."""
         if obs_type != ClothEnv.PARTICLE:
-            raise NotImplementedError("only PARTICLE observations are on the hot path")
+            return super().get_obs(state, eval_min_max_stiff, obs_type)   # DEPTH; anything else raises there
         x = state.x[..., ::10, :]                                          # sample x (N,3) every 10 points
         lead = x.shape[:-2]
         return torch.cat([x.reshape(lead + (-1,)), state.primitive0, state.primitive1], -1)
