@@ -22,14 +22,20 @@ each moves the gradient:
     prim0_grad       the expansion's cotangent on primitive0 zeroed
     chamfer_yx_grad  the goal -> cloth chamfer direction's gradient dropped
     obs_detach       the observation -> policy path cut
+
+The MPM envs whip_rope and pour_water have their own chain further down (MpmStepFn, MpmRefEnv, MPM_MUTATIONS, bar_mpm): the HIP
+step sums with float atomics and is not bit-equal to the oracle, so there each chain (R64: f64 throughout, R32: f32 throughout)
+runs its own forward from the same f32 input values.
 """
 from __future__ import annotations
+
+import math
 
 import numpy as np
 import torch
 import torch.nn.functional as Fn
 
-from .pyoracle import ClothOracle
+from .pyoracle import ClothOracle, MpmOracle
 
 # `/ 3`, `/ 20` as XLA executes them under jit: multiplication by the f32 reciprocal (cloth_env.py:148-163)
 _R3 = np.float32(1) / np.float32(3)
@@ -140,6 +146,11 @@ class ClothRefEnv:
         s.update(leaves)
         return s
 
+    squash = True       # apg.py:185: the cloth envs take sigmoid(tanh sample)
+
+    def obs_of(self, s):
+        return self.get_obs(s["x"], s["primitive0"], s["primitive1"], s["stiffness"])
+
     # -- get_obs (cloth_env.py:94-132) -----------------------------------------------------------------------------------
     def get_obs(self, x, primitive0, primitive1, stiffness):
         lead = x.shape[:-2]
@@ -242,23 +253,27 @@ class PolicyRef:
         return h
 
 
-def squashed_action(logits, eps, min_std=0.001):
-    """sigmoid(NormalTanhDistribution.sample) (apg.py:98-100, :184-186): tanh(loc + (softplus(raw) + min_std) * eps)"""
+def tanh_sample(logits, eps, min_std=0.001):
+    """NormalTanhDistribution.sample (apg.py:98-100, :184): tanh(loc + (softplus(raw) + min_std) * eps)"""
     loc, raw = torch.chunk(logits, 2, dim=-1)
-    return torch.sigmoid(torch.tanh(loc + (Fn.softplus(raw) + min_std) * eps))
+    return torch.tanh(loc + (Fn.softplus(raw) + min_std) * eps)
 
 
 def apg_loss(env_ref, policy, state, noise, action_values=None):
     """-mean(rewards) of len(noise) scanned do_one_step calls.  action_values[t] (f32 [B,6]), when given, are the values the
     actions take (the product's, so that the forward is the product's bit for bit); the gradient flows through the
-    reference policy's own expression.  Without them the chain's action values are used (they must be f32 values)."""
+    reference policy's own expression.  Without them the chain's action values are used (a cloth chain needs f32 values there;
+    the MPM chains always run on their own).  env_ref.obs_of(state) is the observation, env_ref.squash says whether the env takes
+    sigmoid(sample) or the raw tanh sample (apg.py:185; core.py::squashes_actions)."""
     rewards, acts = [], []
     s = state
     for t in range(len(noise)):
-        obs = env_ref.get_obs(s["x"], s["primitive0"], s["primitive1"], s["stiffness"])
+        obs = env_ref.obs_of(s)
         if "obs_detach" in env_ref.mutate:
             obs = obs.detach()
-        a = squashed_action(policy(obs), torch.as_tensor(np.asarray(noise[t]), dtype=env_ref.dtype))
+        a = tanh_sample(policy(obs), torch.as_tensor(np.asarray(noise[t]), dtype=env_ref.dtype))
+        if env_ref.squash:
+            a = torch.sigmoid(a)
         if action_values is not None:
             a = _st(np.asarray(action_values[t], np.float32), a)
         acts.append(a)
@@ -295,3 +310,169 @@ def cloth_reset_state(conf, mask, B, key, dtype=torch.float64):
     t = lambda a: torch.from_numpy(np.ascontiguousarray(np.repeat(np.asarray(a, np.float32)[None], B, 0))).to(dtype)
     return dict(x=t(x), v=t(np.zeros_like(x)), primitive0=t([0.5, 0.5, 0.5, 0.01]), primitive1=t([1.0, 1.0, 1.0, 0.01]),
                 stiffness=t(np.float32(conf.stiffness)), mu=t(np.float32(conf.mu)), cur_step=np.zeros(B, np.int64))
+
+
+# == the MPM envs whip_rope and pour_water ================================================================================
+#   step_diff     mpm_env.py:99-125 focus shift and un-shift, :130-167 scan of simulator.step, nan_to_num, reward :90-94, get_obs :57-76
+#   actions       whip_rope_env.py:108-115, pour_water_env.py:77-90 (`/ 50.0`, `/ 500.0` as XLA executes them: the f32 reciprocal)
+#   simulator     MpmOracle.step_fwd / step_bwd (mpm_simulator.py:413-429, the step-boundary clip :375-411)
+# The product's step sums with float atomics, so nothing here is bit-equal to it: R64 is this chain in f64 throughout, R32 in f32
+# throughout, both from the same f32 input values, and the bar is bar_mpm below.
+_R50 = np.float32(1) / np.float32(50)
+_R500 = np.float32(1) / np.float32(500)
+MPM_MUTATIONS = ("shift_grad", "unshift_pos_grad", "carry_F_detach", "carry_pos_detach", "obs_v_detach", "obs_detach", "reward_mean3")
+# what float-atomic order and the Jacobi SVD add over a sequential f32 sum: twice the largest residual
+# (|HIP - R64|max - KAPPA |R32 - R64|max) / |R64|max measured on the MI355X (8.81e-3, whip_rope's F0 gradient at the reset state, where
+# F is the identity; every other tensor's is negative: tests/test_grad_chain_mpm_gpu.py lists them), rounded up to one digit; never
+# above 2e-2, the relative tolerance the step-level tests hold the 70-substep adjoint to
+FLOOR_MPM = 2e-2
+
+
+def bar_mpm(r64, r32):
+    """what the product's MPM gradient may differ from R64 by: KAPPA |R32 - R64|max + FLOOR_MPM |R64|max"""
+    r64, r32 = (np.asarray(t, np.float64) for t in (r64, r32))
+    return KAPPA * np.abs(r32 - r64).max() + FLOOR_MPM * np.abs(r64).max()
+
+
+class MpmStepFn(torch.autograd.Function):
+    """one simulator.step on the CPU oracle in the dtype of x: (x, v, C, F, J, positions [B,P,S,3], rotations [B,P,S,4],
+    sizes [B,P,3], friction, mu, lamda [B], action [B,6P]) -> (x, v, C, F, J, positions, rotations)"""
+
+    @staticmethod
+    def forward(ctx, ref, x, v, C, F, J, pos, rot, size, friction, mu, lamda, action):
+        dt = x.dtype
+        npdt = np.float64 if dt == torch.float64 else np.float32
+        c = lambda t: np.ascontiguousarray(t.detach().numpy(), dtype=npdt)
+        one = ref.n_prim == 1                   # the oracle takes no primitive axis then
+        p = lambda t: c(t[:, 0]) if one else c(t)
+        st = dict(x=c(x), v=c(v), C=c(C), F=c(F), J=c(J), ppos=p(pos), prot=p(rot), psize=p(size), friction=c(friction), mu=c(mu),
+                  lamda=c(lamda), action=c(action))
+        o = ref.orc.step_fwd(st, nthreads=ref.nthreads)
+        ctx.ref, ctx.st, ctx.dt = ref, st, dt
+        t = lambda a: torch.from_numpy(a).to(dt)
+        q = lambda a: t(a[:, None]) if one else t(a)
+        out = (t(o["x"]), t(o["v"]), t(o["C"]), t(o["F"]), t(o["J"]), q(o["ppos"]), q(o["prot"]))
+        ctx.mark_non_differentiable(out[4], *((out[6],) if ref.position_control else ()))
+        return out
+
+    @staticmethod
+    def backward(ctx, gx, gv, gC, gF, gJ, gpos, grot):
+        ref, st = ctx.ref, ctx.st
+        npdt = st["x"].dtype
+        one = ref.n_prim == 1
+        z = lambda g, like: np.zeros(like.shape, npdt) if g is None else np.ascontiguousarray(g.detach().numpy(), dtype=npdt)
+        p = lambda g, like: z(None if g is None else (g[:, 0] if one else g), like)
+        g = dict(gx=z(gx, st["x"]), gv=z(gv, st["v"]), gC=z(gC, st["C"]), gF=z(gF, st["F"]), gppos=p(gpos, st["ppos"]))
+        if not ref.position_control:
+            g["gprot"] = p(grot, st["prot"])
+        r = ref.orc.step_bwd(st, g, clip=ref.clip, nthreads=ref.nthreads)
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(ctx.dt)
+        q = lambda a: t(a[:, None]) if one else t(a)
+        grot_in = None if ref.position_control else q(r["gprot"])
+        return (None, t(r["gx"]), t(r["gv"]), t(r["gC"]), t(r["gF"]), None, q(r["gppos"]), grot_in, None, t(r["gfriction"]),
+                t(r["gmu"]), t(r["glamda"]), t(r["gaction"]))
+
+
+class MpmRefEnv:
+    """whip_rope's or pour_water's step_diff on the CPU oracle in the chain's dtype.  State: dict x [B,N,3], v, C, F [B,N,3,3],
+    J [B,N], pos [B,P,S,3], rot [B,P,S,4], size [B,P,3], friction, mu, lamda [B] (tensors of the chain's dtype holding f32 values),
+    cur_step (int numpy [B]) and carried (the state came out of a step: the carry mutations apply to it)."""
+
+    squash = False      # apg.py:185: whip_rope and pour_water take the raw tanh sample
+
+    def __init__(self, task, N, goal, n_grid, res, steps, dt, max_steps, p_rho=1.0, gravity=(0, -9.8, 0), material=None, hardness=None,
+                 n_prim=1, sdf="box", prim_friction=0.1, prim_softness=666.0, position_control=True, clip=True, dtype=torch.float64,
+                 nthreads=1, mutate=()):
+        assert task in ("whip_rope", "pour_water"), task
+        self.task, self.dtype, self.nthreads = task, dtype, nthreads
+        self.n_prim, self.position_control, self.clip = n_prim, bool(position_control), bool(clip)
+        self.orc = MpmOracle(N, n_grid=n_grid, res=tuple(res), steps=steps, dt=dt, p_rho=p_rho, gravity=gravity,
+                             position_control=position_control, material=material, hardness=hardness, prim_friction=prim_friction,
+                             prim_softness=prim_softness, n_prim=n_prim, sdf=sdf)
+        self.goal = torch.from_numpy(np.ascontiguousarray(goal, dtype=np.float32)).to(dtype)
+        assert self.goal.shape in ((N, 3), (1, 3))
+        # jnp.array(conf.res) * 0.5 / conf.n_grid (mpm_env.py:102), an f32 value
+        self.center = torch.from_numpy(np.asarray(res, np.float32) * np.float32(0.5) / np.float32(n_grid)).to(dtype)
+        self.max_steps = max_steps
+        self.mutate = set(mutate)
+        assert self.mutate <= set(MPM_MUTATIONS), self.mutate
+
+    @classmethod
+    def from_env(cls, env, dtype=torch.float64, nthreads=1, mutate=()):
+        """the reference of a constructed (and reset) WhipRopeEnv / PourWaterEnv: conf, goal, particle count, material, primitives,
+        SDF kind, per-primitive friction / softness and the clip flag its simulator hands to the step's backward"""
+        conf, sim = env.conf, env.simulator
+        each = lambda v, one: list(v) if len(v) else one
+        return cls(conf.task, sim.n_particles, env.goal.cpu().numpy(), conf.n_grid, conf.res, conf.steps, conf.dt, env.max_steps,
+                   p_rho=conf.p_rho, gravity=conf.gravity, material=np.asarray(sim.material), hardness=np.asarray(sim.h),
+                   n_prim=sim.n_primitive, sdf=sim.sdf_kind, prim_friction=each(sim.prim_friction_each, sim.prim_friction),
+                   prim_softness=each(sim.prim_softness_each, sim.prim_softness), position_control=sim.use_position_control,
+                   clip=sim.clip_grad, dtype=dtype, nthreads=nthreads, mutate=mutate)
+
+    def state_from(self, st, **leaves):
+        """a reference state from an MPMState (device tensors); `leaves` replaces fields by tensors of the chain's dtype"""
+        c = lambda t: torch.from_numpy(t.detach().cpu().numpy()).to(self.dtype)
+        B = st.x.shape[0]
+        stack = lambda k: torch.stack([c(getattr(q, k)) for q in st.primitives], 1)
+        s = dict(x=c(st.x), v=c(st.v), C=c(st.C), F=c(st.F), J=c(st.J), pos=stack("position"), rot=stack("rotation"), size=stack("size"),
+                 friction=c(st.friction).reshape(B), mu=c(st.mu).reshape(B), lamda=c(st.lamda).reshape(B),
+                 cur_step=st.cur_step.cpu().numpy().astype(np.int64), carried=False)
+        s.update(leaves)
+        return s
+
+    # -- get_obs (mpm_env.py:57-76) ------------------------------------------------------------------------------------------
+    def obs_of(self, s):
+        B = s["x"].shape[0]
+        v = s["v"].detach() if "obs_v_detach" in self.mutate else s["v"]
+        return torch.cat([s["x"].reshape(B, -1), v.reshape(B, -1), s["pos"][:, 0].reshape(B, -1)], -1)
+
+    # -- get_primitive_actions (whip_rope_env.py:108-115, pour_water_env.py:77-90) -> [T,B,6P] -----------------------------------
+    def primitive_actions(self, a):
+        if self.task == "whip_rope":
+            a = a + 1e-12
+            a = a * float(_R50)
+            a = torch.cat([a[..., :3], torch.zeros_like(a[..., 3:])], -1)
+            return a[None]
+        a = torch.cat([a, torch.zeros_like(a)], -1)
+        a = torch.cat([a[..., :6] * float(_R500), a[..., 6:]], -1)
+        a = a + 1e-12
+        a = torch.cat([a[..., :1], torch.zeros_like(a[..., :1]), a[..., 2:]], -1)
+        return a[None]
+
+    # -- step_diff (mpm_env.py:130-167) ----------------------------------------------------------------------------------------
+    def step(self, actions, s):
+        """-> (obs, reward, new state, None)"""
+        m = self.mutate
+        n2n = lambda t: torch.where(torch.isfinite(t), t, torch.nan_to_num(t.detach()))      # jnp.nan_to_num: a select
+        x, v, C, F, J, pos, rot = (s[k] for k in ("x", "v", "C", "F", "J", "pos", "rot"))
+        carried = s["carried"]
+        # pre_step :99-114
+        shift = self.center - x.mean(1)
+        shift = torch.stack([shift[:, 0], torch.zeros_like(shift[:, 0]), shift[:, 2]], -1)
+        if "shift_grad" in m:
+            shift = shift.detach()
+        acts = self.primitive_actions(actions)
+        for t in range(acts.shape[0]):                       # lax.scan(simulator.step_jax, ...)
+            if carried:
+                F = F.detach() if "carry_F_detach" in m else F
+                pos = pos.detach() if "carry_pos_detach" in m else pos
+            if t == 0:
+                x, pos = x + shift[:, None], pos + shift[:, None, None]
+            x, v, C, F, J, pos, rot = MpmStepFn.apply(self, x, v, C, F, J, pos, rot, s["size"], s["friction"], s["mu"], s["lamda"], acts[t])
+            carried = True
+        cur = s["cur_step"] + 1
+        assert (cur < self.max_steps).all(), "the chain has no auto_reset: stay inside the episode"
+        # post_step :116-125, nan_to_num :150-154
+        x = x - shift[:, None]
+        pos = pos - shift[:, None, None]
+        if "unshift_pos_grad" in m:
+            pos = pos.detach()
+        x, v, C, F, J = n2n(x), n2n(v), n2n(C), n2n(F), n2n(J)
+        # reward_func :90-94, calc_l2 util.py:156-159
+        sq = (x - self.goal[None]) ** 2
+        reward = math.e ** (-torch.sqrt(sq.mean(-1)).mean(-1) * 10)
+        if "reward_mean3" in m:
+            wrong = math.e ** (-torch.sqrt(sq.sum(-1)).mean(-1) * 10)
+            reward = reward.detach() + (wrong - wrong.detach())
+        new = dict(s, x=x, v=v, C=C, F=F, J=J, pos=pos, rot=rot, cur_step=cur, carried=True)
+        return self.obs_of(new), reward, new, None

@@ -812,6 +812,122 @@ def test_mpm_finish_kernel_matches_torch_with_nonfinite_states(n_prim, focus):
     assert float(gf[0][0, 5, 1]) == 0.0 and float(gf[0][1, 7, 0]) == 0.0 and float(gf[1][2, 3, 2]) == 0.0   # masked by nan_to_num
 
 
+# -- the two glue kernels against an f64 restatement, at the shapes and with the cotangent sets where they can go wrong ----------------
+def _glue_focus_torch(center, x, pos):
+    """pre_step (mpm_env.py:99-114) op by op in the dtype of x -> dict x, shift, p0.."""
+    sh = torch.tensor(center, dtype=x.dtype, device=x.device) - x.mean(1)
+    shift = torch.stack([sh[:, 0], torch.zeros_like(sh[:, 0]), sh[:, 2]], -1)
+    return {"x": x + shift[:, None], "shift": shift, **{f"p{i}": p + shift[:, None] for i, p in enumerate(pos)}}
+
+
+def _glue_finish_torch(x, v, Cm, F, shift, goal, pos):
+    """post_step, nan_to_num (a select, as jnp's), reward_func and get_obs (mpm_env.py:116-125, :150-154, :90-94, :57-76) op by op in
+    the dtype of x -> dict x, v, C, F, reward, obs, p0.."""
+    B = x.shape[0]
+    n2n = lambda t: torch.where(torch.isfinite(t), t, torch.nan_to_num(t.detach()))
+    xo, po = (x - shift[:, None], [p - shift[:, None] for p in pos]) if shift is not None else (x, list(pos))
+    xo, vo, Co, Fo = (n2n(t) for t in (xo, v, Cm, F))
+    reward = math.e ** (-torch.sqrt(((xo - goal[None]) ** 2).mean(-1)).mean(-1) * 10)       # goal [N,3] or the one-row [1,3]
+    obs = torch.cat([xo.reshape(B, -1), vo.reshape(B, -1), po[0].reshape(B, -1)], -1)
+    return {"x": xo, "v": vo, "C": Co, "F": Fo, "reward": reward, "obs": obs, **{f"p{i}": p for i, p in enumerate(po)}}
+
+
+def _glue_compare(run, inputs, cot_keys, tag):
+    """run(dtype-cast leaves, fused) -> dict of outputs.  The kernel's values against the f64 restatement to 1e-6 of each tensor's largest
+    entry (a bound per entry cannot hold for a difference such as c - mean(x), in any f32 implementation); its gradients -- cotangents
+    on `cot_keys` only, every other output unused so that its cotangent reaches the kernel as a null pointer -- no worse than plain f32
+    torch: |kernel - f64|max <= 4 |f32 torch - f64|max + 1e-6 |f64|max."""
+    g = torch.Generator(device=inputs[0].device).manual_seed(9)
+    wts = {}
+
+    def grads(dtype, fusedp):
+        leaves = [None if t is None else t.to(dtype).clone().requires_grad_(True) for t in inputs]
+        outs = run(leaves, fusedp)
+        loss = 0
+        for k in cot_keys:
+            if k not in wts:
+                wts[k] = torch.randn(outs[k].shape, device=outs[k].device, generator=g)
+            loss = loss + (outs[k] * wts[k].to(dtype)).sum()
+        live = [t for t in leaves if t is not None]
+        gr = torch.autograd.grad(loss, live, allow_unused=True)
+        return ({k: t.detach().double() for k, t in outs.items()},
+                [torch.zeros_like(t).double() if q is None else q.double() for t, q in zip(live, gr)])
+
+    ok, gk = grads(torch.float32, True)
+    o32, g32 = grads(torch.float32, False)
+    o64, g64 = grads(torch.float64, False)
+    for k in o64:
+        e, n = float((ok[k] - o64[k]).abs().max()), float(o64[k].abs().max())
+        print(f"GLUE {tag} {k}: |kernel-f64| {e:.2e}  |f64| {n:.2e}  rel {e / n if n else 0:.2e}")
+        assert e <= 1e-6 * n, (tag, k, e, n)
+    for i, (a, b, c) in enumerate(zip(gk, g32, g64)):
+        assert torch.isfinite(a).all(), (tag, i)
+        e, e32, n = float((a - c).abs().max()), float((b - c).abs().max()), float(c.abs().max())
+        print(f"GLUE {tag} grad {i}: |kernel-f64| {e:.2e}  |f32-f64| {e32:.2e}  |f64| {n:.2e}")
+        assert e <= 4 * e32 + 1e-6 * n, (tag, "grad", i, e, e32, n)
+
+
+def _glue_cotangents(only, n_prim, state_keys):
+    last = f"p{n_prim - 1}"                     # the last primitive alone: the others' cotangents are null entries of the pointer array
+    return {"all": list(state_keys) + [f"p{i}" for i in range(n_prim)], "pos": [last]}.get(only, [only])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("N,S,n_prim,only", [(1, 1, 1, "all"), (63, 7, 3, "x"), (256, 300, 4, "shift"), (257, 1, 1, "pos"),
+                                             (1000, 7, 3, "all"), (1000, 300, 4, "pos")])
+def test_mpm_focus_kernel_matches_f64_restatement(N, S, n_prim, only):
+    """ud_mpm_focus_* against pre_step in f64 (the f32 inputs cast up): one particle, fewer than a wave, exactly / one past the 256
+    lanes of its workgroup, several strides; one to four primitives; all cotangents, or only the cloud's, the shift's, or one
+    primitive's."""
+    from unidom_amd.envs.basic import _fused
+    dev = torch.device("cuda", 0)
+    B = 3
+    g = torch.Generator(device=dev).manual_seed(N + S)
+    rnd = lambda *s: torch.randn(s, device=dev, generator=g)
+    x, pos = rnd(B, N, 3) * 0.1 + 0.4, [rnd(B, S, 3) * 0.1 + 0.5 for _ in range(n_prim)]
+    center = (0.25, 0.1, 0.375)
+
+    def run(leaves, fusedp):
+        if fusedp:
+            xs, shift, ps = _fused.mpm_focus(center, leaves[0], leaves[1:])
+            return {"x": xs, "shift": shift, **{f"p{i}": p for i, p in enumerate(ps)}}
+        return _glue_focus_torch(center, leaves[0], leaves[1:])
+
+    _glue_compare(run, [x] + pos, _glue_cotangents(only, n_prim, ("x", "shift")), f"focus N={N} S={S} P={n_prim} {only}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("N,S,n_prim,one_row_goal,focus,only", [
+    (1, 1, 1, False, True, "all"), (63, 7, 3, True, True, "reward"), (256, 300, 4, False, False, "obs"), (257, 1, 1, True, True, "state"),
+    (1000, 7, 3, True, True, "pos"), (1000, 300, 4, False, True, "all"), (257, 7, 1, True, False, "all"), (1000, 7, 3, False, True, "reward"),
+    (1000, 300, 4, True, True, "obs")])
+def test_mpm_finish_kernel_matches_f64_restatement(N, S, n_prim, one_row_goal, focus, only):
+    """ud_mpm_finish_* against the tail of step_diff in f64 (the f32 inputs cast up): particle counts around the 256-particle blocks of
+    the backward (its g_shift atomics across one, two and four blocks), one to four primitives, the goal as [N,3] and as the one-row
+    [1,3] MPMEnv builds when the goal file is missing, with and without a shift, and one cotangent at a time (the null-pointer
+    branches of the backward): the reward's, the observation's, the state's (x, v, C, F) or one primitive's."""
+    from unidom_amd.envs.basic import _fused
+    dev = torch.device("cuda", 0)
+    B = 3
+    g = torch.Generator(device=dev).manual_seed(N + S)
+    rnd = lambda *s: torch.randn(s, device=dev, generator=g)
+    x, v, Cm, F, J = rnd(B, N, 3) * 0.1 + 0.4, rnd(B, N, 3), rnd(B, N, 3, 3), rnd(B, N, 3, 3), rnd(B, N)
+    pos = [rnd(B, S, 3) * 0.1 + 0.5 for _ in range(n_prim)]
+    goal = torch.zeros((1, 3), device=dev) if one_row_goal else rnd(N, 3) * 0.1 + 0.4
+    shift = rnd(B, 3) * 0.05 if focus else None
+
+    def run(leaves, fusedp):
+        xx, vv, CC, FF, sh = leaves[:5]
+        lp = leaves[5:]
+        if fusedp:
+            (xo, vo, Co, Fo, _), reward, obs, po = _fused.mpm_finish(xx, vv, CC, FF, J, sh, goal, lp)
+            return {"x": xo, "v": vo, "C": Co, "F": Fo, "reward": reward, "obs": obs, **{f"p{i}": p for i, p in enumerate(po)}}
+        return _glue_finish_torch(xx, vv, CC, FF, sh, goal.to(xx.dtype), lp)
+
+    keys = ("x", "v", "C", "F") if only == "state" else _glue_cotangents(only, n_prim, ("x", "v", "C", "F", "reward", "obs"))
+    _glue_compare(run, [x, v, Cm, F, shift] + pos, keys, f"finish N={N} S={S} P={n_prim} Q1={one_row_goal} focus={focus} {only}")
+
+
 @pytest.mark.gpu
 def test_mpm_env_done_mirror_and_auto_reset():
     """The env tracks cur_step on the host so that steps on which nobody finishes skip auto_reset (and never wait for the device);
