@@ -1,6 +1,7 @@
-// Pieces of the restructured cloth adjoint (see cloth_fast.hip), shared by the one-workgroup kernel (cloth_fast.hip) and
-// the several-workgroups-per-env kernel (cloth_cluster_bwd.hip).  Including files are compiled with -ffp-contract=fast,
-// except inside grip_own, whose squared distances must carry the forward's bits.
+// Pieces of the restructured cloth adjoint (see cloth_fast.hip), shared by the one-workgroup kernel (cloth_fast_bwd.hip) and
+// the several-workgroups-per-env kernel (cloth_cluster_bwd.hip).  cloth_cluster_bwd.hip is compiled with -ffp-contract=fast,
+// except inside grip_own, whose squared distances must carry the forward's bits; cloth_fast_bwd.hip with contraction off (it
+// writes its fused multiply-adds out and has its own force_pairs_x).
 #pragma once
 #include "cloth_common.h"
 
