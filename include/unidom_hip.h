@@ -299,8 +299,8 @@ int ud_mpm_step_bwd(ud_mpm* h, int B, const void* ckpt, const float* prim_size, 
                     float* g_friction, float* g_mu, float* g_lamda, float* g_action, int* status, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * PlasticineLab-style MLS-MPM, float64, von-Mises plasticity, sticky Sphere primitives (GenORM Torus task,
- * BASELINE config 5) -- replaces TaichiEnv.step -> MPMSimulator.step(is_copy=True) = `substeps` x substep
+ * PlasticineLab-style MLS-MPM, float64, von-Mises plasticity, sticky Sphere and Capsule primitives (GenORM Torus task,
+ * BASELINE config 5; PlasticineLab sim2sim Writer) -- replaces TaichiEnv.step -> MPMSimulator.step(is_copy=True) = `substeps` x substep
  *   GenORM/policy/pbm/plb/engine/mpm_simulator.py:438-449 (step), :256-268 (substep: clear_grid, compute_F_tmp,
  *   svd, p2g :166-195 with compute_von_mises :133-150, forward_kinematics, grid_op :200-232, g2p :234-253),
  *   engine/primitive/primitives.py:17-53 (Sphere), engine/primitive/primive_base.py:118-121,185-192.
@@ -308,7 +308,18 @@ int ud_mpm_step_bwd(ud_mpm* h, int B, const void* ckpt, const float* prim_size, 
  * state, primitive 0's action and position, and per env E, nu, yield_stress (PlasticineLab/sim2sim/plb/engine/
  * mpm_simulator.py:27-29,485-498: get_parameter_grad) and the ground friction (optimize_ground_friction, :57-58).
  * Losses (ud_plb_loss_*): engine/losses/loss.py:112-243 (density, SDF, soft / hard contact, weighted sum).
- * Parity for these entry points is UNPINNED: taichi is absent and the reference ships no recording of this path.
+ * Primitive kinds (prim_kind).  0, the sticky Sphere (primitives.py:17-53): a cell within the soft shell takes the collider's
+ * velocity.  1, the Capsule (primitives.py:55-73) with the base class's contact model (primive_base.py:57-115): the cell g is
+ * taken into the primitive's frame (p = qrot(conj(q) / |q|, g - P_f), p.y += h / 2, p.y -= clamp(p.y, 0, h)); dist =
+ * sqrt(p.p + 1e-14) - r, normal D = qrot(q, p / sqrt(p.p + 1e-14)), influence = min(exp(-dist softness), 1); the cell is active
+ * when (softness > 0 and influence > 0.1) or dist <= 0; an active cell's velocity u becomes cv + w (1 - influence) + t' influence
+ * with cv the collider velocity, w = u - cv, t = w - min(w.D, 0) D and t' = t / |t| max(0, |t| + (w.D) prim_friction) where
+ * w.D < 0 (|t| = sqrt(t.t + 1e-8)).  Its adjoint holds the two branch decisions constant and reaches u, P_f (through p, dist,
+ * D, influence, cv) and P_{f+1}; orientation, height, radius, friction and softness are not leaves.  The contact loss takes the
+ * Capsule's distance.  The orientation is a handle constant (only primitive 0 is actuated, three action dimensions).
+ * A handle with a Capsule, or with an action_scale other than (1, 1, 1), runs the multi-kernel path only.
+ * Parity for these entry points is UNPINNED: taichi is absent and the reference ships no recording of this path; the torch
+ * restatements (oracle/twin/plb_twin_torch.py, tests/plb_prim_twin.py for the Capsule) are the specification the kernels are held to.
  * ------------------------------------------------------------------------------------------------ */
 typedef struct ud_plb ud_plb;
 
@@ -319,7 +330,7 @@ typedef struct {
   double dt;             /* 0.5e-4 / (quality * 0.5)                  :21 */
   double gravity[3];     /* SIMULATOR.gravity (the kernel applies x30, :205) */
   double ground_friction;
-  int n_primitives;      /* 1 or 2 Spheres; only primitive 0 is actuated (3 action dims) */
+  int n_primitives;      /* 1 or 2 primitives (Spheres unless prim_kind says otherwise); only primitive 0 is actuated (3 action dims) */
   double radius[2];
   double lower_bound[3], upper_bound[3];   /* primitive xyz_limit */
   int grid_ckpt_cells;   /* 0: ud_plb_step_bwd runs p2g again for every substep (substep_grad recomputes the whole substep,
@@ -343,6 +354,14 @@ typedef struct {
                             the restatement at their sizes) */
   int sort_every;        /* the handle orders each env's particles by grid cell internally (invisible at this boundary) on the first
                             call and every sort_every-th forward call after it; 0 = 8; negative = never */
+  /* Everything below: zero = the handle of before these fields existed (sticky Spheres, action scale 1) */
+  int prim_kind[2];      /* 0 sticky Sphere, 1 Capsule (radius[i], capsule_h[i], prim_rot[i], prim_friction[i]); else UD_ERR_INVALID.  A handle
+                            with a Capsule runs the multi-kernel path (path = 0 picks it; path = 2: UD_ERR_UNSUPPORTED) */
+  double capsule_h[2];   /* Capsule: length of the axis segment (along the primitive's y), >= 0; radius[i] > 0 */
+  double prim_rot[2][4]; /* Capsule: constant orientation (w, x, y, z); all four zero = identity, else |q| > 0.9 as the reference asserts */
+  double prim_friction[2];   /* Capsule: Coulomb friction of the contact (primitive cfg.friction) */
+  double action_scale[3];    /* primitive 0: v = clip(action, -1, 1) * action_scale / substeps (set_velocity); all zero = (1, 1, 1).  Any
+                                other value: multi-kernel path, as with a Capsule */
 } ud_plb_conf;
 
 int ud_plb_create(const ud_plb_conf* conf, ud_plb** out);

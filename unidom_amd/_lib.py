@@ -50,7 +50,9 @@ class ud_plb_conf(C.Structure):
     _fields_ = [("n_particles", C.c_int), ("n_grid", C.c_int), ("substeps", C.c_int), ("dt", C.c_double),
                 ("gravity", C.c_double * 3), ("ground_friction", C.c_double), ("n_primitives", C.c_int),
                 ("radius", C.c_double * 2), ("lower_bound", C.c_double * 3), ("upper_bound", C.c_double * 3),
-                ("grid_ckpt_cells", C.c_int), ("max_envs", C.c_int), ("path", C.c_int), ("lanes", C.c_int), ("sort_every", C.c_int)]
+                ("grid_ckpt_cells", C.c_int), ("max_envs", C.c_int), ("path", C.c_int), ("lanes", C.c_int), ("sort_every", C.c_int),
+                ("prim_kind", C.c_int * 2), ("capsule_h", C.c_double * 2), ("prim_rot", (C.c_double * 4) * 2),
+                ("prim_friction", C.c_double * 2), ("action_scale", C.c_double * 3)]
 
 
 def build(force: bool = False) -> str:

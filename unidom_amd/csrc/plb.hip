@@ -4,13 +4,14 @@
 //   mpm_simulator.py  step :438-449, substep :256-268 = clear_grid :69-79, compute_F_tmp :91-94, svd :96-99,
 //                     p2g :166-195 (compute_von_mises :133-150), grid_op :200-232, g2p :234-253
 //   primitive/primitives.py Sphere.sdf/collider_v/collide :17-53 ; primitive/primive_base.py forward_kinematics :118-121,
-//                     set_velocity :185-192
+//                     set_velocity :185-192; on a handle with a Capsule (plb_prim.h) Primitive.collide :57-115, Capsule :55-73
 // The reference drives 7 Taichi kernels per substep from Python over a dense n_grid^3 grid, one env per process.
 // Here B envs run batched: per substep  clear (touched cells only) -> p2g -> grid op (touched cells only) -> g2p,
 // the p2g scatter is summed per workgroup in an LDS cell table (ds_add_f64) and flushed with one
 // global_atomic_add_f64 per distinct cell and component; the grid lives dense in HBM (n_grid^3 x 4 doubles per env)
 // but only cells on the per-env active list are ever read, written or cleared.  No MFMA (scatter / stencil work).
 // ti.svd (third party) is replaced by a one-sided Jacobi SVD in registers.  Parity: UNPINNED (see the header).
+#include <cmath>
 #include <cstdlib>
 #include "plb_device.h"
 
@@ -160,8 +161,9 @@ __global__ void __launch_bounds__(256) plb_p2g(PlbArgs a) {
   plb_p2g_body<LANES>(a, tg, b, p, qi, p < c.N, x, v, Cm, F, s_key, s_val);
 }
 
-// grid_op (:200-232) over the touched cells
-__global__ void __launch_bounds__(256) plb_grid(PlbArgs a) {
+// grid_op (:200-232) over the touched cells.  GEN: the handle has a general primitive (plb_prim.h), fixed at create
+template <bool GEN>
+__global__ void __launch_bounds__(256) plb_grid(PlbArgs a, PlbPrimArg<GEN> pr) {
   const int b = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x;
   const PlbConst& c = a.c;
   const int cur = a.lb, prev = cur ^ 1;
@@ -182,7 +184,7 @@ __global__ void __launch_bounds__(256) plb_grid(PlbArgs a) {
     o[0] = cell[0]; o[1] = cell[1]; o[2] = cell[2]; o[3] = cell[3];
   }
   double vv[3];
-  plb_grid_cell(c, lin, cell[0], cell + 1, a.w.pos + ((long)b * (c.S + 1) + a.f) * c.np * 3, a.softness + b * c.np, vv);
+  plb_grid_cell_any<GEN>(c, pr, lin, cell[0], cell + 1, a.w.pos + ((long)b * (c.S + 1) + a.f) * c.np * 3, a.softness + b * c.np, vv);
   cell[1] = vv[0]; cell[2] = vv[1]; cell[3] = vv[2];
 }
 
@@ -374,14 +376,14 @@ __global__ void __launch_bounds__(1024) plb_sort(PlbArgs a, const double* x, int
 // state into the history's slot 0 in the call's spatial order; block 0 of each env also runs the prologue (primitive positions of the whole
 // step, both list counts).  order: the handle's current spatial order (arena), copied to this call's perm (the checkpoint's, for the adjoint).
 __global__ void __launch_bounds__(256) plb_pack(PlbArgs a, const double* x, const double* v, const double* Cm, const double* F, const int* order,
-                                                const double* prim_pos, const double* action) {
+                                                const double* prim_pos, const double* action, PlbScale sc) {
   const int b = blockIdx.y, p = blockIdx.x * blockDim.x + threadIdx.x;
   const PlbConst& c = a.c;
   if (blockIdx.x == 0) {
-    if (threadIdx.x < c.np * 3) {   // pos[s+1] = clamp(pos[s] + v), v = clip(action) * scale / substeps for primitive 0; one thread per coordinate
+    if (threadIdx.x < c.np * 3) {   // pos[s+1] = clamp(pos[s] + v), v = clip(action) * scale / substeps for primitive 0 (set_velocity, primive_base.py:185-192); one thread per coordinate
       const int pi = threadIdx.x / 3, d = threadIdx.x % 3;
       double* P = a.w.pos + (long)b * (c.S + 1) * c.np * 3;
-      const double pv = (pi == 0) ? fmin(fmax(action[b * 3 + d], -1.0), 1.0) * 1.0 / (double)c.S : 0.0;
+      const double pv = (pi == 0) ? fmin(fmax(action[b * 3 + d], -1.0), 1.0) * sc.s[d] / (double)c.S : 0.0;
       double cur = prim_pos[(long)b * c.np * 3 + pi * 3 + d];
       P[pi * 3 + d] = cur;
       for (int s = 0; s < c.S; ++s) {
@@ -505,6 +507,38 @@ int ud_plb_create(const ud_plb_conf* conf, ud_plb** out) {
   for (int d = 0; d < 3; ++d) { c.g30dt[d] = conf->dt * conf->gravity[d] * 30; c.lo[d] = conf->lower_bound[d]; c.hi[d] = conf->upper_bound[d]; }
   c.fric = conf->ground_friction;
   c.radius[0] = conf->radius[0]; c.radius[1] = conf->radius[1];
+  // general primitives (plb_prim.h) and the action scale: a zeroed block is today's handle -- sticky Spheres, scale (1, 1, 1)
+  const bool zero_scale = conf->action_scale[0] == 0 && conf->action_scale[1] == 0 && conf->action_scale[2] == 0;
+  for (int d = 0; d < 3; ++d) h->ascale.s[d] = zero_scale ? 1.0 : conf->action_scale[d];
+  const bool unit_scale = h->ascale.s[0] == 1.0 && h->ascale.s[1] == 1.0 && h->ascale.s[2] == 1.0;
+  for (int pi = 0; pi < c.np; ++pi) {
+    const int kind = conf->prim_kind[pi];
+    if (kind != 0 && kind != 1) { ud::set_error("ud_plb_create: prim_kind[%d] = %d (0 Sphere, 1 Capsule)", pi, kind); delete h; return UD_ERR_INVALID; }
+    ud::PlbPrim& pr = h->prim;
+    pr.kind[pi] = kind; pr.h[pi] = conf->capsule_h[pi]; pr.mu[pi] = conf->prim_friction[pi];
+    const double* q = conf->prim_rot[pi];
+    const double n2 = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
+    const bool ident = q[0] == 0 && q[1] == 0 && q[2] == 0 && q[3] == 0;
+    if (kind == 1) {
+      h->gen = true;
+      if (!ident && !(std::sqrt(n2) > 0.9)) { ud::set_error("ud_plb_create: |prim_rot[%d]| = %g (the reference asserts > 0.9; all zero = identity)", pi, std::sqrt(n2)); delete h; return UD_ERR_INVALID; }
+      if (!(conf->capsule_h[pi] >= 0) || !(conf->radius[pi] > 0)) {
+        ud::set_error("ud_plb_create: Capsule %d needs capsule_h >= 0 and radius > 0 (h = %g, r = %g)", pi, conf->capsule_h[pi], conf->radius[pi]); delete h; return UD_ERR_INVALID;
+      }
+    }
+    const double nrm = std::sqrt(n2);
+    for (int k = 0; k < 4; ++k) {
+      pr.q[pi][k] = ident ? (k == 0 ? 1.0 : 0.0) : q[k];
+      pr.qi[pi][k] = ident ? (k == 0 ? 1.0 : 0.0) : (k == 0 ? q[k] : -q[k]) / nrm;
+    }
+  }
+  // The persistent kernels (plb_cluster.hip) hold the sticky Sphere and the unit action scale only: any other handle runs the multi-kernel path
+  const bool mk_only = h->gen || !unit_scale;
+  if (conf->path == 2 && mk_only) {
+    ud::set_error("ud_plb_create: path = 2 (persistent) has no %s: such a handle runs the multi-kernel path (path = 0 or 1)",
+                  h->gen ? "Capsule primitive (prim_kind = 1)" : "action_scale other than (1, 1, 1)");
+    delete h; return UD_ERR_UNSUPPORTED;
+  }
   h->G = (long)c.n_grid * c.n_grid * c.n_grid;
   h->cap = (int)std::min<long>(h->G, (long)27 * c.N);
   c.gck = conf->grid_ckpt_cells > 0 ? (int)std::min<long>(h->cap, (long)conf->grid_ckpt_cells * c.N) : 0;
@@ -513,7 +547,7 @@ int ud_plb_create(const ud_plb_conf* conf, ud_plb** out) {
   (void)hipFuncSetAttribute((const void*)ud::plb_sort, hipFuncAttributeMaxDynamicSharedMemorySize, ud::PLB_SORT_MAX * 8);
   // Which kernels this handle runs is decided here, once: the persistent launch per step call (plb_cluster.hip) where all parts of a
   // launch can be resident and the exchange grids fit, else the multi-kernel path.  path = 1 / 2 force one (2: an error if it cannot run).
-  int per = conf->path == 1 ? 0 : plb_cluster_plan(h, conf->max_envs);
+  int per = (conf->path == 1 || mk_only) ? 0 : plb_cluster_plan(h, conf->max_envs);
   if (conf->path == 2 && per < 1) {
     ud::set_error("ud_plb_create: path = 2 (persistent) does not fit this configuration (parts per env %d, substeps %d)", h->cl.W, c.S);
     delete h; return UD_ERR_UNSUPPORTED;
@@ -602,7 +636,7 @@ int ud_plb_step_fwd(ud_plb* h, int B, const double* x, const double* v, const do
   // not fill the chip, 1 beyond; ud_plb_conf.lanes forces one mapping (how the tests reach all three at their sizes)
   const int lanes = h->lanes ? h->lanes : (((long)B * h->c.N <= 16000) ? 8 : (((long)B * h->c.N < 100000) ? 4 : 1));
   const dim3 gq((lanes * h->c.N + 255) / 256, B);
-  hipLaunchKernelGGL(ud::plb_pack, gp, blk, 0, st, a, x, v, C, F, sorted ? (const int*)h->order : (const int*)nullptr, prim_pos, action);
+  hipLaunchKernelGGL(ud::plb_pack, gp, blk, 0, st, a, x, v, C, F, sorted ? (const int*)h->order : (const int*)nullptr, prim_pos, action, h->ascale);
   // Per substep: plb_grid(f), then ONE particle launch: g2p(f) -> p2g(f + 1) (plb_g2p_p2g); p2g(0) opens the step, g2p(S - 1) closes it.
   const bool fused = true;
   const int S = h->c.S;
@@ -619,7 +653,8 @@ int ud_plb_step_fwd(ud_plb* h, int B, const double* x, const double* v, const do
   UD_PLB_LAUNCH(plb_p2g);
   for (int f = 0; f < S; ++f) {
     set(f);
-    hipLaunchKernelGGL(ud::plb_grid, gc, blk, 0, st, a);
+    if (h->gen) hipLaunchKernelGGL(ud::plb_grid<true>, gc, blk, 0, st, a, ud::PlbPrimArg<true>{h->prim});
+    else hipLaunchKernelGGL(ud::plb_grid<false>, gc, blk, 0, st, a, ud::PlbPrimArg<false>{});
     if (fused && f + 1 < S) {
       UD_PLB_LAUNCH(plb_g2p_p2g);
     } else {

@@ -11,7 +11,8 @@
 // Structure: the forward call keeps every substep's particle state, the primitive trajectory and the spatial order in a
 // caller-owned checkpoint (ud_plb_ckpt_bytes); the backward walks the substeps in reverse, per substep
 //   plb_p2g (recompute, plb.hip) -> plb_grid_keep (v_out beside (m, mv)) -> plb_g2p_adj (scatter of the v_out cotangent,
-//   x cotangent through the weights) -> plb_grid_adj (cell by cell: boundary / friction / sticky sphere / normalisation)
+//   x cotangent through the weights) -> plb_grid_adj (cell by cell: boundary / friction / sticky sphere or, on a handle with
+//   a Capsule, the frictional soft contact of plb_prim.h / normalisation)
 //   -> plb_p2g_adj (gather; stress, von Mises return mapping, SVD and F update in reverse; E / nu / yield-stress sums)
 //   -> plb_adj_clear,
 // over the touched cells only, like the forward, and with the forward's two lane mappings (four lanes per particle while
@@ -24,7 +25,8 @@
 namespace ud {
 
 // ---- grid op, kept: v_out of every touched cell into buffer 1 (buffer 0 keeps (m, mv)) ---------------------------------
-__global__ void __launch_bounds__(256) plb_grid_keep(PlbArgs a) {
+template <bool GEN>   // the handle has a general primitive (plb_prim.h)
+__global__ void __launch_bounds__(256) plb_grid_keep(PlbArgs a, PlbPrimArg<GEN> pr) {
   const int b = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x;
   const PlbConst& c = a.c;
   const int cur = a.lb, prev = cur ^ 1;
@@ -56,7 +58,7 @@ __global__ void __launch_bounds__(256) plb_grid_keep(PlbArgs a) {
     cell = plb_buf(a, cur, b) + lin * 4;
   }
   double vv[3];
-  plb_grid_cell(c, lin, cell[0], cell + 1, a.w.pos + ((long)b * (c.S + 1) + a.f) * c.np * 3, a.softness + b * c.np, vv);
+  plb_grid_cell_any<GEN>(c, pr, lin, cell[0], cell + 1, a.w.pos + ((long)b * (c.S + 1) + a.f) * c.np * 3, a.softness + b * c.np, vv);
   double* out = plb_vout(a, b) + lin * 4;   // never cleared: read only at cells this launch has just written
   out[0] = vv[0]; out[1] = vv[1]; out[2] = vv[2];
 }
@@ -174,12 +176,14 @@ __global__ void __launch_bounds__(256) plb_g2p_adj(PlbArgs a, int gs_in) {
 }
 
 // ---- grid op adjoint (:200-232 in reverse), one touched cell per lane -------------------------------------------------
-__global__ void __launch_bounds__(256) plb_grid_adj(PlbArgs a) {
+template <bool GEN>
+__global__ void __launch_bounds__(256) plb_grid_adj(PlbArgs a, PlbPrimArg<GEN> pr) {
   const int b = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x;
   const PlbConst& c = a.c;
   // per-env cotangents (sticky-sphere positions, ground friction): summed over the wave, one atomic per wave and word -- one per cell
   // put every cell near a sphere on the same few words of its env (cf. lg_grid_adj_tile, mpm_large.hip)
   double qs[2][3] = {{0, 0, 0}, {0, 0, 0}}, gfric = 0;
+  [[maybe_unused]] double q0[2][3] = {{0, 0, 0}, {0, 0, 0}};   // GEN: what the cell sends to gpos[f], independent of qs
   const bool inlist = t < min(a.w.count[a.lb * a.B + b], a.cap);
   const long lin = inlist ? a.w.list[((long)a.lb * a.B + b) * a.cap + t] : 0;
   const double* cell = plb_buf(a, a.lb, b) + lin * 4;
@@ -187,7 +191,8 @@ __global__ void __launch_bounds__(256) plb_grid_adj(PlbArgs a) {
   if (inlist) {
     const double g[3] = {ga[0], ga[1], ga[2]};
     double gout[4];
-    plb_grid_cell_adj(c, lin, cell[0], cell + 1, g, a.w.pos + ((long)b * (c.S + 1) + a.f) * c.np * 3, a.softness + b * c.np, gout, qs, gfric);
+    if constexpr (GEN) plb_grid_cell_adj_gen(c, pr.p, lin, cell[0], cell + 1, g, a.w.pos + ((long)b * (c.S + 1) + a.f) * c.np * 3, a.softness + b * c.np, gout, q0, qs, gfric);
+    else plb_grid_cell_adj(c, lin, cell[0], cell + 1, g, a.w.pos + ((long)b * (c.S + 1) + a.f) * c.np * 3, a.softness + b * c.np, gout, qs, gfric);
     ga[0] = gout[0]; ga[1] = gout[1]; ga[2] = gout[2]; ga[3] = gout[3];
   }
   double* gpos = a.w.gpos + ((long)b * (c.S + 1) + a.f) * c.np * 3;
@@ -195,6 +200,16 @@ __global__ void __launch_bounds__(256) plb_grid_adj(PlbArgs a) {
 #pragma unroll
   for (int pi = 0; pi < 2; ++pi) {
     if (pi >= c.np) break;
+    if constexpr (GEN) {
+      if (!__any(qs[pi][0] != 0.0 || qs[pi][1] != 0.0 || qs[pi][2] != 0.0 || q0[pi][0] != 0.0 || q0[pi][1] != 0.0 || q0[pi][2] != 0.0)) continue;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const double q = plb_wave_sum(qs[pi][k]), p = plb_wave_sum(q0[pi][k]);
+        if (lead && q != 0.0) atomicAdd(gpos + c.np * 3 + pi * 3 + k, q);
+        if (lead && p != 0.0) atomicAdd(gpos + pi * 3 + k, p);
+      }
+      continue;
+    }
     if (!__any(qs[pi][0] != 0.0 || qs[pi][1] != 0.0 || qs[pi][2] != 0.0)) continue;   // wave-uniform
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -346,8 +361,8 @@ __global__ void __launch_bounds__(256) plb_adj_unpack(PlbArgs a, int slot, doubl
   for (int d = 0; d < 9; ++d) { gC[o9 + d] = g[(6 + d) * c.Np + p]; gF[o9 + d] = g[(15 + d) * c.Np + p]; }
 }
 
-// forward_kinematics.grad + set_action in reverse: pos[s+1] = clamp(pos[s] + pv), pv = clip(action, -1, 1) / S for primitive 0
-__global__ void plb_adj_epilogue(PlbArgs a, const double* action, double* g_prim_pos0, double* g_action, double* g_E, double* g_nu, double* g_ys, double* g_fric) {
+// forward_kinematics.grad + set_action in reverse: pos[s+1] = clamp(pos[s] + pv), pv = clip(action, -1, 1) * scale / S for primitive 0
+__global__ void plb_adj_epilogue(PlbArgs a, PlbScale sc, const double* action, double* g_prim_pos0, double* g_action, double* g_E, double* g_nu, double* g_ys, double* g_fric) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= a.Bcall) return;   // g_action, g_E, ... are the caller's [Bcall] arrays
   const PlbConst& c = a.c;
@@ -356,7 +371,7 @@ __global__ void plb_adj_epilogue(PlbArgs a, const double* action, double* g_prim
   for (int pi = 0; pi < c.np; ++pi)
     for (int d = 0; d < 3; ++d) {
       const double raw = (pi == 0) ? action[b * 3 + d] : 0.0;
-      const double pv = (pi == 0) ? fmin(fmax(raw, -1.0), 1.0) / (double)c.S : 0.0;
+      const double pv = (pi == 0) ? fmin(fmax(raw, -1.0), 1.0) * sc.s[d] / (double)c.S : 0.0;
       double gpv = 0.0;
       for (int s = c.S - 1; s >= 0; --s) {
         const double un = P[(s * c.np + pi) * 3 + d] + pv;
@@ -366,7 +381,7 @@ __global__ void plb_adj_epilogue(PlbArgs a, const double* action, double* g_prim
         gpv += g;
       }
       if (g_prim_pos0) g_prim_pos0[((long)b * c.np + pi) * 3 + d] = G[pi * 3 + d];
-      if (pi == 0 && g_action) g_action[b * 3 + d] = (raw >= -1.0 && raw <= 1.0) ? gpv / (double)c.S : 0.0;
+      if (pi == 0 && g_action) g_action[b * 3 + d] = (raw >= -1.0 && raw <= 1.0) ? gpv * sc.s[d] / (double)c.S : 0.0;
     }
   if (g_E) g_E[b] = a.w.gpar[b * 4];
   if (g_nu) g_nu[b] = a.w.gpar[b * 4 + 1];
@@ -418,7 +433,30 @@ __global__ void __launch_bounds__(256) plb_loss_grid(long G, const double* gm, c
 
 // contact sums per primitive pi: soft :117-135 lred[b][4 + 2 pi] += sum w(d), lred[b][5 + 2 pi] += sum d w(d);
 // hard :120-124: a minimum, taken through the ordered-integer view of the non-negative double (lred[b][8 + pi], preset to +inf)
-__global__ void __launch_bounds__(256) plb_loss_contact(PlbConst c, const double* x, const double* prim_pos, int soft, double* lred) {
+// distance of a particle to primitive pi (before the max with 0): the sphere's, or on a GEN handle the Capsule's (plb_prim.h); its gradient in x is
+// grad / den (the sphere's is left as the quotient the callers have always formed: d / len)
+template <bool GEN>
+__device__ __forceinline__ double plb_loss_dist(const PlbConst& c, const PlbPrimArg<GEN>& pr, int pi, const double* xp, const double* pp, double* grad, double* den) {
+  const double d[3] = {xp[0] - pp[0], xp[1] - pp[1], xp[2] - pp[2]};
+  if constexpr (GEN) {
+    if (pr.p.kind[pi] == 1) {
+      double pl[3], p[3], pass_y;
+      const double len = plb_capsule_local(pr.p, pi, d, pl, p, pass_y);
+      if (grad) {
+        const double zero[3] = {0, 0, 0};
+        plb_capsule_local_adj(pr.p, pi, p, len, pass_y, 1.0, zero, zero, grad);
+        *den = 1.0;
+      }
+      return len - c.radius[pi];
+    }
+  }
+  const double len = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + 1e-14);
+  if (grad) { grad[0] = d[0]; grad[1] = d[1]; grad[2] = d[2]; *den = len; }
+  return len - c.radius[pi];
+}
+
+template <bool GEN>
+__global__ void __launch_bounds__(256) plb_loss_contact(PlbConst c, PlbPrimArg<GEN> pr, const double* x, const double* prim_pos, int soft, double* lred) {
   __shared__ double sh[4];
   const int b = blockIdx.y, p = blockIdx.x * blockDim.x + threadIdx.x;
   for (int pi = 0; pi < c.np; ++pi) {
@@ -426,8 +464,7 @@ __global__ void __launch_bounds__(256) plb_loss_contact(PlbConst c, const double
     if (p < c.N) {
       const double* xp = x + ((long)b * c.N + p) * 3;
       const double* pp = prim_pos + ((long)b * c.np + pi) * 3;
-      const double d0 = xp[0] - pp[0], d1 = xp[1] - pp[1], d2 = xp[2] - pp[2];
-      dij = fmax(sqrt(d0 * d0 + d1 * d1 + d2 * d2 + 1e-14) - c.radius[pi], 0.0);
+      dij = fmax(plb_loss_dist<GEN>(c, pr, pi, xp, pp, nullptr, nullptr), 0.0);
       sw = 1.0 / (1.0 + dij * dij * 10000.0);
     }
     if (soft) {
@@ -458,7 +495,8 @@ __global__ void plb_loss_finish(PlbConst c, int B, int soft, const double* wts, 
 }
 
 // loss adjoint: g_x and g_prim_pos.  Needs gm (grid mass) and lred (the forward's sums) of the same inputs.
-__global__ void __launch_bounds__(256) plb_loss_bwd_kernel(PlbConst c, long G, int soft, const double* wts, const double* x, const double* prim_pos,
+template <bool GEN>
+__global__ void __launch_bounds__(256) plb_loss_bwd_kernel(PlbConst c, PlbPrimArg<GEN> pr, long G, int soft, const double* wts, const double* x, const double* prim_pos,
                                                           const double* td, const double* tsdf, const double* gm, const double* lred,
                                                           const double* g_loss, double* g_x, double* g_pp) {
   const int b = blockIdx.y, p = blockIdx.x * blockDim.x + threadIdx.x;
@@ -485,9 +523,8 @@ __global__ void __launch_bounds__(256) plb_loss_bwd_kernel(PlbConst c, long G, i
   const double* r = lred + b * 16;
   for (int pi = 0; pi < c.np; ++pi) {
     const double* pp = prim_pos + ((long)b * c.np + pi) * 3;
-    const double d0 = xp[0] - pp[0], d1 = xp[1] - pp[1], d2 = xp[2] - pp[2];
-    const double len = sqrt(d0 * d0 + d1 * d1 + d2 * d2 + 1e-14);
-    const double raw = len - c.radius[pi];
+    double dn[3], len;   // gradient of the distance in x: dn / len
+    const double raw = plb_loss_dist<GEN>(c, pr, pi, xp, pp, dn, &len);
     const double dij = fmax(raw, 0.0);
     double gd = 0;   // d loss / d dij for this particle
     if (soft) {
@@ -501,7 +538,7 @@ __global__ void __launch_bounds__(256) plb_loss_bwd_kernel(PlbConst c, long G, i
       gd = (dij == md) ? gl * wts[0] * 2 * md : 0.0;   // the minimum passes its cotangent to the argmin (ties: every one of them)
     }
     if (raw > 0.0 && gd != 0.0) {
-      const double q[3] = {gd * d0 / len, gd * d1 / len, gd * d2 / len};
+      const double q[3] = {gd * dn[0] / len, gd * dn[1] / len, gd * dn[2] / len};
 #pragma unroll
       for (int k = 0; k < 3; ++k) { gx[k] += q[k]; if (g_pp) atomicAdd(g_pp + ((long)b * c.np + pi) * 3 + k, -q[k]); }
     }
@@ -549,11 +586,13 @@ int ud_plb_step_bwd(ud_plb* h, int B, const void* ckpt, const double* softness, 
   for (int f = S - 1; f >= 0; --f) {
     a.f = f; a.epoch = h->epoch++; a.hs_in = f; a.hs_out = f + 1; a.lb = f & 1; a.ls = a.lb; a.lprev = a.lb ^ 1; a.lnext = a.lprev;
     if (!never_recompute) ud::plb_launch_p2g(a, lanes, lanes > 1 ? gq : gp, st);   // recompute (m, mv) (rewrites F[f + 1] with the same values); envs with a checkpointed substep leave at once
-    hipLaunchKernelGGL(ud::plb_grid_keep, gc, blk, 0, st, a);
+    if (h->gen) hipLaunchKernelGGL(ud::plb_grid_keep<true>, gc, blk, 0, st, a, ud::PlbPrimArg<true>{h->prim});
+    else hipLaunchKernelGGL(ud::plb_grid_keep<false>, gc, blk, 0, st, a, ud::PlbPrimArg<false>{});
     if (lanes == 8) hipLaunchKernelGGL(ud::plb_g2p_adj<8>, gq, blk, 0, st, a, (f + 1) & 1);
     else if (lanes == 4) hipLaunchKernelGGL(ud::plb_g2p_adj<4>, gq, blk, 0, st, a, (f + 1) & 1);
     else hipLaunchKernelGGL(ud::plb_g2p_adj<1>, gp, blk, 0, st, a, (f + 1) & 1);
-    hipLaunchKernelGGL(ud::plb_grid_adj, gc, blk, 0, st, a);
+    if (h->gen) hipLaunchKernelGGL(ud::plb_grid_adj<true>, gc, blk, 0, st, a, ud::PlbPrimArg<true>{h->prim});
+    else hipLaunchKernelGGL(ud::plb_grid_adj<false>, gc, blk, 0, st, a, ud::PlbPrimArg<false>{});
     if (lanes == 8) hipLaunchKernelGGL(ud::plb_p2g_adj<8>, gqa, dim3(128), 0, st, a, (f + 1) & 1);
     else if (lanes == 4) hipLaunchKernelGGL(ud::plb_p2g_adj<4>, gqa, dim3(128), 0, st, a, (f + 1) & 1);
     else hipLaunchKernelGGL(ud::plb_p2g_adj<1>, gpa, dim3(128), 0, st, a, (f + 1) & 1);
@@ -562,7 +601,7 @@ int ud_plb_step_bwd(ud_plb* h, int B, const void* ckpt, const double* softness, 
   hipLaunchKernelGGL(ud::plb_adj_clear, gc, blk, 0, st, a);
   hipLaunchKernelGGL(ud::plb_adj_reset_counts, dim3((B + 63) / 64), dim3(64), 0, st, a);
   hipLaunchKernelGGL(ud::plb_adj_unpack, gp, blk, 0, st, a, 0, g_x0, g_v0, g_C0, g_F0);
-  hipLaunchKernelGGL(ud::plb_adj_epilogue, dim3((B + 63) / 64), dim3(64), 0, st, a, action, g_prim_pos0, g_action, g_E, g_nu, g_yield_stress, g_ground_friction);
+  hipLaunchKernelGGL(ud::plb_adj_epilogue, dim3((B + 63) / 64), dim3(64), 0, st, a, h->ascale, action, g_prim_pos0, g_action, g_E, g_nu, g_yield_stress, g_ground_friction);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { ud::set_error("ud_plb_step_bwd: %s", hipGetErrorString(e)); return UD_ERR_HIP; }
   return UD_OK;
@@ -579,7 +618,10 @@ static int plb_loss_common(ud_plb* h, int B, const double* x, const double* prim
   hipLaunchKernelGGL(ud::plb_loss_mass, gp, blk, 0, st, c, h->G, x, h->gm);
   const int gb = (int)std::min<long>((h->G + 255) / 256, 1024);
   hipLaunchKernelGGL(ud::plb_loss_grid, dim3(gb, B), blk, 0, st, h->G, (const double*)h->gm, target_density, target_sdf, h->lred);
-  if (c.np > 0) hipLaunchKernelGGL(ud::plb_loss_contact, gp, blk, 0, st, c, x, prim_pos, soft_contact, h->lred);
+  if (c.np > 0) {
+    if (h->gen) hipLaunchKernelGGL(ud::plb_loss_contact<true>, gp, blk, 0, st, c, ud::PlbPrimArg<true>{h->prim}, x, prim_pos, soft_contact, h->lred);
+    else hipLaunchKernelGGL(ud::plb_loss_contact<false>, gp, blk, 0, st, c, ud::PlbPrimArg<false>{}, x, prim_pos, soft_contact, h->lred);
+  }
   return UD_OK;
 }
 
@@ -603,8 +645,10 @@ int ud_plb_loss_bwd(ud_plb* h, int B, const double* x, const double* prim_pos, c
   if (rc) return rc;
   if (g_prim_pos) { if (hipMemsetAsync(g_prim_pos, 0, (size_t)B * h->c.np * 3 * 8, st) != hipSuccess) { ud::set_error("ud_plb_loss_bwd: memset failed"); return UD_ERR_HIP; } }
   const dim3 blk(256), gp((h->c.N + 255) / 256, B);
-  hipLaunchKernelGGL(ud::plb_loss_bwd_kernel, gp, blk, 0, st, h->c, h->G, soft_contact, weights, x, prim_pos, target_density, target_sdf,
-                     (const double*)h->gm, (const double*)h->lred, g_loss, g_x, g_prim_pos);
+  if (h->gen) hipLaunchKernelGGL(ud::plb_loss_bwd_kernel<true>, gp, blk, 0, st, h->c, ud::PlbPrimArg<true>{h->prim}, h->G, soft_contact, weights, x, prim_pos,
+                                 target_density, target_sdf, (const double*)h->gm, (const double*)h->lred, g_loss, g_x, g_prim_pos);
+  else hipLaunchKernelGGL(ud::plb_loss_bwd_kernel<false>, gp, blk, 0, st, h->c, ud::PlbPrimArg<false>{}, h->G, soft_contact, weights, x, prim_pos,
+                          target_density, target_sdf, (const double*)h->gm, (const double*)h->lred, g_loss, g_x, g_prim_pos);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { ud::set_error("ud_plb_loss_bwd: %s", hipGetErrorString(e)); return UD_ERR_HIP; }
   return UD_OK;

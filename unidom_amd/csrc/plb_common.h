@@ -1,6 +1,7 @@
 // Shared pieces of the PlasticineLab-style f64 MLS-MPM kernels: forward (plb.hip), adjoint and losses (plb_adj.hip).
 #pragma once
 #include "common.h"
+#include "plb_prim.h"
 
 namespace ud {
 
@@ -260,6 +261,54 @@ __device__ __forceinline__ void plb_grid_cell(const PlbConst& c, long lin, doubl
   }
 }
 
+struct PlbScale { double s[3]; };   // action scale of primitive 0 (set_velocity: v = clip(action) * scale / substeps)
+
+// The same for a handle with a general primitive (plb_prim.h): kind 1 collides as Primitive.collide does, kind 0 sticks as above.  A function
+// of its own, and plb_grid_cell left to the letter: the persistent kernels inline that one at the edge of their register budget, and a
+// Sphere-only handle runs exactly the code it always ran.
+__device__ __forceinline__ void plb_grid_cell_gen(const PlbConst& c, const PlbPrim& pr, long lin, double m, const double* mv, const double* P0, const double* soft,
+                                                  double* vv) {
+  vv[0] = 0.0; vv[1] = 0.0; vv[2] = 0.0;
+  if (!(m > 1e-12)) return;
+  const int n = c.n_grid;
+  const int I[3] = {(int)(lin / ((long)n * n)), (int)((lin / n) % n), (int)(lin % n)};
+#pragma unroll
+  for (int k = 0; k < 3; ++k) vv[k] = (1.0 / m) * mv[k] + c.g30dt[k];
+  const double gp[3] = {I[0] * c.dx, I[1] * c.dx, I[2] * c.dx};
+  const double* P1 = P0 + c.np * 3;
+  for (int pi = 0; pi < c.np; ++pi) {
+    if (pr.kind[pi] == 1) { plb_collide(pr, pi, c.radius[pi], c.dt, gp, P0 + pi * 3, P1 + pi * 3, soft[pi], vv); continue; }
+    const double d0 = gp[0] - P0[pi * 3], d1 = gp[1] - P0[pi * 3 + 1], d2 = gp[2] - P0[pi * 3 + 2];
+    const double dist = sqrt(d0 * d0 + d1 * d1 + d2 * d2 + 1e-14) - c.radius[pi];
+    const double sf = soft[pi];
+    const double infl = fmin(exp(-dist * sf), 1.0);
+    if (((sf > 0 && infl > 0.1) || dist <= 0.001) && sf > 0) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) vv[k] = (P1[pi * 3 + k] - P0[pi * 3 + k]) / c.dt;
+    }
+  }
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    if (I[d] < 3 && vv[d] < 0) {
+      if (d != 1 || c.fric == 0) vv[d] = 0;
+      else if (c.fric < 10) {
+        const double lin_ = vv[1] + 1e-30;
+        const double vit[3] = {vv[0] - I[0] * 1e-30, vv[1] - lin_ - I[1] * 1e-30, vv[2] - I[2] * 1e-30};
+        const double lit = sqrt(vit[0] * vit[0] + vit[1] * vit[1] + vit[2] * vit[2] + 1e-8);
+        const double s = fmax(1.0 + c.fric * lin_ / lit, 0.0);
+        vv[0] = s * (vit[0] + I[0] * 1e-30); vv[2] = s * (vit[2] + I[2] * 1e-30); vv[1] = 0;
+      } else { vv[0] = 0; vv[1] = 0; vv[2] = 0; }
+    }
+    if (I[d] > n - 3 && vv[d] > 0) vv[d] = 0;
+  }
+}
+template <bool GEN>
+__device__ __forceinline__ void plb_grid_cell_any(const PlbConst& c, const PlbPrimArg<GEN>& pr, long lin, double m, const double* mv, const double* P0,
+                                                  const double* soft, double* vv) {
+  if constexpr (GEN) plb_grid_cell_gen(c, pr.p, lin, m, mv, P0, soft, vv);
+  else plb_grid_cell(c, lin, m, mv, P0, soft, vv);
+}
+
 void plb_launch_p2g(const PlbArgs& a, int lanes, dim3 grid, hipStream_t st);   // plb_p2g<lanes> (plb.hip), for the adjoint's recompute
 
 }  // namespace ud
@@ -287,6 +336,9 @@ struct ud_plb {
   int sort_B = 0, sort_age = 0;   // envs the spatial order covers, forward calls since it was computed
   int lanes = 0;            // multi-kernel path: lanes per particle forced by the conf (0 = by launch size)
   int sort_every = 8;       // forward calls between two sorts (<= 0: never sort)
+  bool gen = false;         // some primitive is not a sticky Sphere: the GEN = true kernels of the multi-kernel path (plb_prim.h)
+  ud::PlbPrim prim{};
+  ud::PlbScale ascale{{1.0, 1.0, 1.0}};
   PlbCluster cl;
 };
 // every arena of the handle, once, at create (no allocation and no host synchronisation in any step call)

@@ -303,4 +303,99 @@ __device__ __forceinline__ void plb_grid_cell_adj(const PlbConst& c, long lin, d
   ga[3] = -(g[0] * mv[0] + g[1] * mv[1] + g[2] * mv[2]) * im * im;
 }
 
+// ---- the same for a handle with a general primitive (plb_prim.h; a function of its own for the reason given at plb_grid_cell_gen).  A cell sends
+// two independent vectors per primitive: q1[pi] adds to gpos[f + 1][pi], q0[pi] adds to gpos[f][pi] (a sticky sphere sends q0 = -q1).
+__device__ __forceinline__ void plb_grid_cell_adj_gen(const PlbConst& c, const PlbPrim& pr, long lin, double m, const double* mv, const double* gin, const double* P0,
+                                                      const double* soft, double* ga, double q0[2][3], double q1[2][3], double& gfric) {
+  ga[0] = 0; ga[1] = 0; ga[2] = 0; ga[3] = 0;
+  if (!(m > 1e-12)) return;
+  double g[3] = {gin[0], gin[1], gin[2]};
+  const int n = c.n_grid;
+  const int I[3] = {(int)(lin / ((long)n * n)), (int)((lin / n) % n), (int)(lin % n)};
+  const double* P1 = P0 + c.np * 3;
+  // forward, keeping the velocity that entered each boundary stage
+  double vv[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) vv[k] = (1.0 / m) * mv[k] + c.g30dt[k];
+  bool stick[2] = {false, false};
+  const double gp[3] = {I[0] * c.dx, I[1] * c.dx, I[2] * c.dx};
+  double uin[2][3];        // velocity entering primitive pi
+  for (int pi = 0; pi < c.np; ++pi) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) uin[pi][k] = vv[k];
+    if (pr.kind[pi] == 1) { stick[pi] = plb_collide(pr, pi, c.radius[pi], c.dt, gp, P0 + pi * 3, P1 + pi * 3, soft[pi], vv); continue; }
+    const double d0 = gp[0] - P0[pi * 3], d1 = gp[1] - P0[pi * 3 + 1], d2 = gp[2] - P0[pi * 3 + 2];
+    const double dist = sqrt(d0 * d0 + d1 * d1 + d2 * d2 + 1e-14) - c.radius[pi];
+    const double sf = soft[pi];
+    const double infl = fmin(exp(-dist * sf), 1.0);
+    if (((sf > 0 && infl > 0.1) || dist <= 0.001) && sf > 0) {
+      stick[pi] = true;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) vv[k] = (P1[pi * 3 + k] - P0[pi * 3 + k]) / c.dt;
+    }
+  }
+  double vin[3][3];        // velocity entering stage d
+  int kind[3];             // 0 nothing, 1 component zeroed, 2 friction, 3 all zeroed
+  bool hiz[3];
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) vin[d][k] = vv[k];
+    kind[d] = 0;
+    if (I[d] < 3 && vv[d] < 0) {
+      if (d != 1 || c.fric == 0) { vv[d] = 0; kind[d] = 1; }
+      else if (c.fric < 10) {
+        const double lin_ = vv[1] + 1e-30;
+        const double vit[3] = {vv[0] - I[0] * 1e-30, vv[1] - lin_ - I[1] * 1e-30, vv[2] - I[2] * 1e-30};
+        const double lit = sqrt(vit[0] * vit[0] + vit[1] * vit[1] + vit[2] * vit[2] + 1e-8);
+        const double s = fmax(1.0 + c.fric * lin_ / lit, 0.0);
+        vv[0] = s * (vit[0] + I[0] * 1e-30); vv[2] = s * (vit[2] + I[2] * 1e-30); vv[1] = 0;
+        kind[d] = 2;
+      } else { vv[0] = 0; vv[1] = 0; vv[2] = 0; kind[d] = 3; }
+    }
+    hiz[d] = (I[d] > n - 3 && vv[d] > 0);
+    if (hiz[d]) vv[d] = 0;
+  }
+  // reverse
+#pragma unroll
+  for (int d = 2; d >= 0; --d) {
+    if (hiz[d]) g[d] = 0;
+    if (kind[d] == 1) g[d] = 0;
+    else if (kind[d] == 3) { g[0] = 0; g[1] = 0; g[2] = 0; }
+    else if (kind[d] == 2) {
+      const double* u = vin[d];
+      const double lin_ = u[1] + 1e-30;
+      const double vit[3] = {u[0] - I[0] * 1e-30, u[1] - lin_ - I[1] * 1e-30, u[2] - I[2] * 1e-30};
+      const double lit = sqrt(vit[0] * vit[0] + vit[1] * vit[1] + vit[2] * vit[2] + 1e-8);
+      const double arg = 1.0 + c.fric * lin_ / lit;
+      const double s = fmax(arg, 0.0);
+      const double gs = g[0] * (vit[0] + I[0] * 1e-30) + g[2] * (vit[2] + I[2] * 1e-30);
+      double gvit[3] = {g[0] * s, 0.0, g[2] * s};
+      double glin = 0, glit = 0;
+      if (arg > 0) { glin = gs * c.fric / lit; glit = -gs * c.fric * lin_ / (lit * lit); gfric += gs * lin_ / lit; }
+#pragma unroll
+      for (int k = 0; k < 3; ++k) gvit[k] += glit * vit[k] / lit;
+      glin -= gvit[1];                       // vit_y = v_y - lin - I_y 1e-30
+      g[0] = gvit[0]; g[2] = gvit[2]; g[1] = gvit[1] + glin;
+    }
+  }
+#pragma unroll
+  for (int pi = 1; pi >= 0; --pi) {
+    if (!(pi < c.np && stick[pi])) continue;
+    if (pr.kind[pi] == 1) {      // the forward of this primitive again from the velocity that entered it, then in reverse
+      PlbCollide k;
+      plb_collide_eval(pr, pi, c.radius[pi], c.dt, gp, P0 + pi * 3, P1 + pi * 3, soft[pi], uin[pi], k);
+      double gu[3];
+      plb_collide_adj(pr, pi, c.dt, k, soft[pi], g, gu, q0[pi], q1[pi]);
+      g[0] = gu[0]; g[1] = gu[1]; g[2] = gu[2];
+    } else {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) { q1[pi][k] = g[k] / c.dt; q0[pi][k] = -(g[k] / c.dt); g[k] = 0; }
+    }
+  }
+  const double im = 1.0 / m;
+  ga[0] = g[0] * im; ga[1] = g[1] * im; ga[2] = g[2] * im;
+  ga[3] = -(g[0] * mv[0] + g[1] * mv[1] + g[2] * mv[2]) * im * im;
+}
+
 }  // namespace ud

@@ -1,7 +1,9 @@
-"""PlbSimulator -- host mirror of GenORM's Taichi MPMSimulator + Primitives + Loss for the Torus task (float64).
+"""PlbSimulator -- host mirror of GenORM's Taichi MPMSimulator + Primitives + Loss for the Torus task and PlasticineLab's
+sim2sim Writer task (float64).
 
 Mirrors /root/reference/GenORM/policy/pbm/plb/engine/mpm_simulator.py (constants :14-32, step :438-449 in copy
-mode, substep_grad :271-289), the two Sphere primitives of envs/torus.yml and engine/losses/loss.py:112-243; the
+mode, substep_grad :271-289), the two Sphere primitives of envs/torus.yml, the Capsule of PlasticineLab/sim2sim/plb/envs/
+writer.yml (engine/primitive/primive_base.py:57-115, primitives.py:55-73) and engine/losses/loss.py:112-243; the
 physics runs in libunidom_hip.so (csrc/plb.hip forward, csrc/plb_adj.hip adjoint + losses).  The reference holds one
 env per process in Taichi fields and differentiates with ti.Tape; here B independent envs are batched in one call and
 `step` / `compute_loss` are torch.autograd Functions over the forward / adjoint kernel pairs, so
@@ -49,6 +51,36 @@ class PlbConf:
     prim_radius = (0.025, 0.025)
     prim_init_pos = ((0.475, 0.05, 0.5), (0.5, 0.55, 0.5))
     lower_bound = (0.0, 0.0, 0.0)
+    upper_bound = (1.0, 1.0, 1.0)
+    # per primitive (ud_plb_conf, include/unidom_hip.h): kind 0 = sticky Sphere, 1 = Capsule of height prim_h, constant orientation
+    # prim_rot (w, x, y, z) and contact friction prim_friction; action_scale: v = clip(action) * scale / substeps (primitive 0)
+    prim_kind = (0, 0)
+    prim_h = (0.0, 0.0)
+    prim_rot = ((1.0, 0.0, 0.0, 0.0), (1.0, 0.0, 0.0, 0.0))
+    prim_friction = (0.0, 0.0)
+    action_scale = (1.0, 1.0, 1.0)
+    softness = 666.0         # Primitive cfg default, set_softness()
+
+
+class WriterConf(PlbConf):
+    """PlasticineLab/sim2sim/plb/envs/writer.yml over sim2sim/plb/config/default_config.py: a 10 000-particle box on the floor
+    (ground_friction 100: the floor stops what touches it) and one frictionless Capsule.  Runs the multi-kernel path."""
+    n_particles = 10000
+    E = 5e3
+    nu = 0.35
+    yield_stress = 50.0
+    gravity = (0.0, -1.0, 0.0)
+    ground_friction = 100.0
+    box_width = (0.3, 0.1, 0.3)
+    box_init_pos = (0.5, 0.05, 0.5)
+    prim_kind = (1,)
+    prim_radius = (0.03,)
+    prim_h = (0.06,)
+    prim_init_pos = ((0.5, 0.13, 0.5),)
+    prim_rot = ((0.0, 0.0, 0.0, 1.0),)
+    prim_friction = (0.0,)
+    action_scale = (0.01, 0.01, 0.01)
+    lower_bound = (0.0, 0.05, 0.0)
     upper_bound = (1.0, 1.0, 1.0)
 
 
@@ -151,12 +183,18 @@ class PlbSimulator:
         # kernel selection, fixed at create (include/unidom_hip.h): path 0 = the library's choice (one persistent launch per step call
         # where it fits), 1 = multi-kernel, 2 = persistent; lanes / sort_every: diagnostics of the multi-kernel path / the spatial order
         self.path, self.lanes, self.sort_every = (int(getattr(cfg, k, 0)) for k in ("path", "lanes", "sort_every"))
+        P = self.n_primitive
+        pad = lambda seq, fill: (list(seq)[:P] + [fill] * 2)[:2]
+        self.prim_kind = tuple(int(k) for k in pad(cfg.prim_kind, 0))[:P]
+        rot = (C.c_double * 4 * 2)(*[(C.c_double * 4)(*q) for q in pad(cfg.prim_rot, (0.0, 0.0, 0.0, 0.0))])
         cc = _lib.ud_plb_conf(
             n_particles=self.n_particles, n_grid=self.n_grid, substeps=self.substeps, dt=self.dt,
             gravity=(C.c_double * 3)(*cfg.gravity), ground_friction=float(cfg.ground_friction), n_primitives=self.n_primitive,
             radius=(C.c_double * 2)(*(list(cfg.prim_radius) + [0.0])[:2]),
             lower_bound=(C.c_double * 3)(*cfg.lower_bound), upper_bound=(C.c_double * 3)(*cfg.upper_bound),
-            grid_ckpt_cells=int(self.grid_ckpt_cells), max_envs=int(batch_size), path=self.path, lanes=self.lanes, sort_every=self.sort_every)
+            grid_ckpt_cells=int(self.grid_ckpt_cells), max_envs=int(batch_size), path=self.path, lanes=self.lanes, sort_every=self.sort_every,
+            prim_kind=(C.c_int * 2)(*pad(cfg.prim_kind, 0)), capsule_h=(C.c_double * 2)(*pad(cfg.prim_h, 0.0)), prim_rot=rot,
+            prim_friction=(C.c_double * 2)(*pad(cfg.prim_friction, 0.0)), action_scale=(C.c_double * 3)(*cfg.action_scale))
         self._h = C.c_void_p()
         self.profile = None    # {"fwd": [], "bwd": []}: HIP-event pairs around every step call, on its stream (bench.py)
         self.ground_friction_grad = None   # [B], accumulated by backward() (optimize_ground_friction.grad); reset it by hand
@@ -194,7 +232,7 @@ class PlbSimulator:
             raise _lib.UnidomError(_lib.lib().ud_last_error().decode())
 
     def reset(self) -> PlbState:
-        """Shapes.add_box with np.random.seed(0) (shape_maker.py:21-31,49-58) + primitive init (torus.yml)."""
+        """Shapes.add_box with np.random.seed(0) (shape_maker.py:21-31,49-58) + primitive init (torus.yml / writer.yml)."""
         cfg, B, dev = self.cfg, self.batch_size, self.device
         st = np.random.get_state()
         np.random.seed(0)
@@ -207,7 +245,7 @@ class PlbSimulator:
                         C=torch.zeros((B, N, 3, 3), dtype=torch.float64, device=dev),
                         F=rep(torch.eye(3, dtype=torch.float64, device=dev)[None].repeat(N, 1, 1)),
                         prim_pos=rep(f64(cfg.prim_init_pos)),
-                        softness=torch.full((B, self.n_primitive), 666.0, dtype=torch.float64, device=dev),   # set_softness()
+                        softness=torch.full((B, self.n_primitive), float(cfg.softness), dtype=torch.float64, device=dev),   # set_softness()
                         E=torch.full((B,), float(cfg.E), dtype=torch.float64, device=dev),
                         nu=torch.full((B,), float(cfg.nu), dtype=torch.float64, device=dev),
                         yield_stress=torch.full((B,), float(cfg.yield_stress), dtype=torch.float64, device=dev))
