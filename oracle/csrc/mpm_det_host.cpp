@@ -100,4 +100,13 @@ int oc_mpm_det_forward(int B, int N, int n_grid, const int* res, int steps, floa
   return 0;
 }
 
+// svd3 and ud_expf of this build (UD_HOST_BUILD: the deterministic mode's arithmetic) on their own, for tests/test_devfn_cpu.py and the
+// bit-for-bit comparison with the device's exact build in tests/test_devfn_gpu.py.  A, U, Vh [n][9] row-major, S [n][3].
+void oc_dev_svd3_f32(long n, const float* A, float* U, float* S, float* Vh) {
+  for (long i = 0; i < n; ++i) ud::svd3(A + i * 9, U + i * 9, S + i * 3, Vh + i * 9);
+}
+void oc_dev_expf(long n, const float* x, float* y) {
+  for (long i = 0; i < n; ++i) y[i] = ud::ud_expf(x[i]);
+}
+
 }  // extern "C"

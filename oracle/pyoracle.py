@@ -267,6 +267,30 @@ def svd3(A):
     return U, S, Vh
 
 
+def dev_svd3_f32(A):
+    """svd3 of unidom_amd/csrc/mpm_device.h in the host build of the deterministic mode's source (csrc/mpm_det_host.cpp): A [n, 3, 3] f32."""
+    A = np.ascontiguousarray(A, dtype=np.float32).reshape(-1, 3, 3)
+    U, S, Vh = np.empty_like(A), np.empty((A.shape[0], 3), np.float32), np.empty_like(A)
+    lib().oc_dev_svd3_f32(C.c_long(A.shape[0]), _p(A), _p(U), _p(S), _p(Vh))
+    return U, S, Vh
+
+
+def dev_dsvd3_f64(A):
+    """dsvd3 of unidom_amd/csrc/plb_svd.h compiled for the host (csrc/plb_svd_host.cpp: IEEE stand-ins for the hardware seeds): A [n, 3, 3] f64."""
+    A = np.ascontiguousarray(A, dtype=np.float64).reshape(-1, 3, 3)
+    U, S, Vh = np.empty_like(A), np.empty((A.shape[0], 3), np.float64), np.empty_like(A)
+    lib().oc_dev_dsvd3_f64(C.c_long(A.shape[0]), _p(A), _p(U), _p(S), _p(Vh))
+    return U, S, Vh
+
+
+def dev_expf(x):
+    """ud_expf of unidom_amd/csrc/mpm_collide.h in the host build: the deterministic mode's plain-IEEE exp, elementwise on f32."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    y = np.empty_like(x)
+    lib().oc_dev_expf(C.c_long(x.size), _p(x), _p(y))
+    return y
+
+
 class PlbOracle:
     """CPU restatement (f64, dense grid) of the Taichi PlasticineLab forward step (GenORM Torus, BASELINE config 5).
     PARITY UNPINNED (see oracle/csrc/plb_oracle.hpp)."""

@@ -322,10 +322,11 @@ _R50 = np.float32(1) / np.float32(50)
 _R500 = np.float32(1) / np.float32(500)
 MPM_MUTATIONS = ("shift_grad", "unshift_pos_grad", "carry_F_detach", "carry_pos_detach", "obs_v_detach", "obs_detach", "reward_mean3")
 # what float-atomic order and the Jacobi SVD add over a sequential f32 sum: twice the largest residual
-# (|HIP - R64|max - KAPPA |R32 - R64|max) / |R64|max measured on the MI355X (8.81e-3, whip_rope's F0 gradient at the reset state, where
-# F is the identity; every other tensor's is negative: tests/test_grad_chain_mpm_gpu.py lists them), rounded up to one digit; never
-# above 2e-2, the relative tolerance the step-level tests hold the 70-substep adjoint to
-FLOOR_MPM = 2e-2
+# (|HIP - R64|max - KAPPA |R32 - R64|max) / |R64|max measured on the MI355X, rounded up to one digit, never above 2e-2 (the relative
+# tolerance the step-level tests hold the 70-substep adjoint to) and never raised.  It was 2e-2 while svd3 left its sweeps too early
+# (residual 8.81e-3 on whip_rope's F0 gradient at the reset state, F = I); with the exit at round-off level that residual is -4.04e-3 and
+# every asserted tensor's is negative (tests/test_grad_chain_mpm_gpu.py lists them): KAPPA |R32 - R64| alone covers the product.
+FLOOR_MPM = 0.0
 
 
 def bar_mpm(r64, r32):

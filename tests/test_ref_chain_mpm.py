@@ -195,18 +195,20 @@ def test_each_planted_mistake_moves_a_compared_gradient_far_past_the_gpu_bar(dem
     gradients (actions, x0, v0, F0, positions) over 2 steps with random cotangents of weight 1e-3 on obs and the final state and 1 on
     the rewards ("step": the weights of the GPU test), and over 1 step with weight 1 everywhere ("step_w1"), in R64, R32 and R64
     with each entry of MPM_MUTATIONS planted.  Each mistake must move at least one of them by >= 10 x bar_mpm(R64, R32), the bar
-    tests/test_grad_chain_mpm_gpu.py holds the product to, evaluated with the final FLOOR_MPM = 2e-2 (where a gradient that is
-    wrong altogether scores 50).  Measured, in bars, the first compared gradient found past 10 (step, then apg, then step_w1; rope, then bowls):
-        shift_grad        19.6  bowls/step_w1/x
-        unshift_pos_grad  50    rope/step/pos
-        carry_F_detach    29.1  rope/step/F
-        carry_pos_detach  47.2  rope/step/pos
-        obs_v_detach      44.6  rope/step/actions
-        obs_detach        14.4  rope/apg/flat
-        reward_mean3      37.4  rope/apg/flat
-    shift_grad is the weak one: the step is translation-equivariant up to grid artefacts, so the shift's cotangent on the way in and
-    the one on the way out cancel but for those; with the GPU test's weights it moves the rope's x0 gradient by 1 to 8 bars only
-    (T = 1 to 3), and reaches 10 only where obs and the final state weigh as much as the reward."""
+    tests/test_grad_chain_mpm_gpu.py holds the product to, evaluated with the final FLOOR_MPM = 0 (the bar is KAPPA |R32 - R64|max
+    alone, 1e-5 to 1e-3 of these gradients).  Measured, in bars, the first compared gradient found past 10 (step, then apg, then step_w1; rope, then bowls):
+        shift_grad        6.67e+03  rope/step/actions
+        unshift_pos_grad  1.15e+05  rope/step/pos
+        carry_F_detach    2.31e+04  rope/step/actions
+        carry_pos_detach  1.09e+05  rope/step/pos
+        obs_v_detach      8.21e+04  rope/step/actions
+        obs_detach        1.7e+03   rope/apg/flat
+        reward_mean3      1.47e+04  rope/step/actions
+    (with FLOOR_MPM at 2e-2, as it was while svd3 left its sweeps too early, these were 14 to 50 bars, shift_grad reaching 10 only on
+    bowls/step_w1/x.)
+    With the floor at 2e-2 shift_grad was the weak one: the step is translation-equivariant up to grid artefacts, so the shift's cotangent on the way in and
+    the one on the way out cancel but for those; with the GPU test's weights it moved the rope's x0 gradient by 1 to 8 of those bars
+    only (T = 1 to 3), and reached 10 only where obs and the final state weigh as much as the reward."""
     kw = {"rope": dict(ks=[0, 40]), "bowls": {}}
     base = {}
 

@@ -49,8 +49,8 @@ __device__ __forceinline__ float div_rn_prepped(float a, float d, float rd) {
   q = __builtin_fmaf(e, rd, q);
   return (a == 0.0f) ? q0 : q;          // (+-0) * rd is the correctly signed zero; the FMA chain would return +0
 }
-// the same without the select: a zero numerator returns +0 whatever its sign (callers that only add the quotient to a running sum or
-// subtract it from one do not see the difference).  Also checked for |a| in [2^-100, 2^100), |d| in [2^-24, 2^24) (check_exact_div 33 100 24):
+// the same without the select: a zero numerator returns a zero, but not always with IEEE's sign (-0 / 3 gives +0; callers that only add the
+// quotient to a running sum or subtract it from one do not see the difference).  Also checked for |a| in [2^-100, 2^100), |d| in [2^-24, 2^24) (check_exact_div 33 100 24):
 // what the sequence needs is a normal quotient and residuals above the denormal floor, not these particular windows.
 __device__ __forceinline__ float div_rn_prepped_nz(float a, float d, float rd) {
   float q = a * rd;

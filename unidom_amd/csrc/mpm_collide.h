@@ -76,9 +76,10 @@ __device__ __forceinline__ float div_rte(float a, const DivDen& q) { return (flo
 #endif
 
 // exp for the softness falloff.  The fast kernels take the platform's expf; the deterministic mode's builds (UD_MPM_EXACT on the device,
-// UD_HOST_BUILD for the same-order CPU checker) need the SAME bits from hipcc and from the host compiler: range reduction and a degree-6
-// polynomial in plain IEEE operations (neither build contracts), scaled by an exact ldexp.  Within 2 ulp of expf on the range that reaches
-// it; results below the normal range are flushed to zero (influence 1e-38 either way).
+// UD_HOST_BUILD for the same-order CPU checker) need the SAME bits from hipcc and from the host compiler: range reduction and a degree-7
+// polynomial in plain IEEE operations (neither build contracts), scaled by an exact ldexp.  Measured within 1 ulp of the correctly rounded exp on [-87, 88.7)
+// (tests/test_devfn_cpu.py holds it to 2 on [-87, 0], the range that reaches it; at degree 6 it was 3); results below the normal range are
+// flushed to zero (influence 1e-38 either way).
 #if defined(UD_MPM_EXACT) || defined(UD_HOST_BUILD)
 __device__ __forceinline__ float ud_expf(float x) {
   if (!(x < 88.7f)) return x != x ? x : INFINITY;
@@ -86,7 +87,8 @@ __device__ __forceinline__ float ud_expf(float x) {
   const float kf = rintf(x * 1.44269504f);
   float r = x - kf * 0.693359375f;            // ln 2 in two pieces: the first has 9 significant bits, its product with |k| <= 128 is exact
   r = r - kf * -2.12194440e-4f;
-  float p = 1.3888889e-3f;
+  float p = 1.9841270e-4f;                    // 1 / 7!: without this term the truncation alone is 1 ulp at |r| = ln 2 / 2 (3 ulp in all, measured)
+  p = p * r + 1.3888889e-3f;
   p = p * r + 8.3333333e-3f;
   p = p * r + 4.1666668e-2f;
   p = p * r + 1.6666667e-1f;

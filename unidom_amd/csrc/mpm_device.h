@@ -74,8 +74,9 @@ __device__ __forceinline__ void m_mul_at(const float* A, const float* B, float* 
     const float be = a[q] * a[q] + a[3 + q] * a[3 + q] + a[6 + q] * a[6 + q];                                \
     const float ga = a[p] * a[q] + a[3 + p] * a[3 + q] + a[6 + p] * a[6 + q];                                \
     const float ab_ = al * be, gg_ = ga * ga;                                                                \
-    const bool rot = !done && gg_ > 2.25e-16f * ab_;        /* |ga| > 1.5e-8 sqrt(al be) */                  \
-    any_rot |= gg_ > 1e-8f * ab_;                           /* |ga| > 1e-4 sqrt(al be) */                    \
+    const bool big_ = gg_ > 1e-13f * ab_;                   /* |ga| > 3.2e-7 sqrt(al be) */                  \
+    const bool rot = !done && big_;                                                                          \
+    any_rot |= big_;                                                                                         \
     const float g2_ = rot ? ga + ga : 1.f, d_ = be - al;                                                     \
     const float h_ = UD_FSQRT(d_ * d_ + g2_ * g2_);                                                          \
     float t = fabsf(g2_) * UD_FRCP(fabsf(d_) + h_);                                                          \
@@ -109,11 +110,15 @@ __device__ __forceinline__ void svd3(const float* A, float* U, float* S, float* 
   float a[9], vv[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
 #pragma unroll
   for (int i = 0; i < 9; ++i) a[i] = A[i];
-  // Cyclic Jacobi converges quadratically: a sweep whose three normalised off-diagonal products were all below 1e-4 leaves them below
-  // 1e-8 -- under the rotation threshold, so every later sweep would be the identity.  Leave after such a sweep, per WAVE on the device
-  // (when none of its lanes had a larger product): a rope's F is near a rotation and its particles are done in two sweeps; the chain of
-  // dependent rotations is the longest serial stretch of the pre-pass, which at one or two waves per SIMD is what a launch waits for
-  // (lanes probe).
+  // One threshold, at round-off level: a pair is rotated while its normalised column product |a_p . a_q| / (|a_p| |a_q|) is above 3.2e-7
+  // (a few f32 eps; the computed product itself carries ~1e-7 of rounding, so rotating on anything smaller is rotating on noise), and a
+  // matrix leaves the iteration after a sweep that rotated none of its pairs: its columns are then orthogonal to round-off and U = A V / S
+  // is orthonormal to round-off.  The exit is per WAVE on the device (when none of its lanes rotated): the chain of dependent rotations is
+  // the longest serial stretch of the pre-pass, which at one or two waves per SIMD is what a launch waits for (lanes probe).
+  // The threshold must NOT be derived from quadratic convergence ("products below 1e-4 after a sweep leave them below 1e-8": an earlier
+  // version did, and left at 1e-4): inside a cluster of singular values, A = Q (c I + E) with small E, Jacobi works on E alone, off(E) / |E| is
+  // O(1) and one sweep squares nothing -- a rope at rest is exactly that case, and U came out non-orthogonal at 1e-4, S wrong by up to
+  // 60 % of the strain (tests/test_devfn_cpu.py holds the factors to 16 eps on those families).
   bool done = false;
 #pragma unroll 1
   for (int sweep = 0; sweep < UD_SVD_SWEEPS; ++sweep) {   // 4 sweeps reach f32 round-off for |F - I| up to O(1) (measured)
