@@ -316,8 +316,22 @@ int ud_mpm_step_bwd(ud_mpm* h, int B, const void* ckpt, const float* prim_size, 
  * with cv the collider velocity, w = u - cv, t = w - min(w.D, 0) D and t' = t / |t| max(0, |t| + (w.D) prim_friction) where
  * w.D < 0 (|t| = sqrt(t.t + 1e-8)).  Its adjoint holds the two branch decisions constant and reaches u, P_f (through p, dist,
  * D, influence, cv) and P_{f+1}; orientation, height, radius, friction and softness are not leaves.  The contact loss takes the
- * Capsule's distance.  The orientation is a handle constant (only primitive 0 is actuated, three action dimensions).
+ * Capsule's distance.  Without rot_state the orientation is a handle constant (only primitive 0 is actuated, three action dimensions).
  * A handle with a Capsule, or with an action_scale other than (1, 1, 1), runs the multi-kernel path only.
+ * Rotating primitives (rot_state; the *_rot entry points).  Every primitive carries a rotation (w, x, y, z) beside its position, as the
+ * reference's Primitive does (primive_base.py:31-38), turned once per substep (:117-121):
+ *   a = clip(action, -1, 1) (its cotangent passes at equality and is zero outside);
+ *   kinds 0 and 1:  v = a[0:3] action_scale / substeps, w = a[3:6] action_scale_w / substeps (0 with three action dimensions and for
+ *     primitive 1);  pos[f+1] = clamp(pos[f] + v, lower_bound, upper_bound);  rot[f+1] = qmul(w2quat(w), rot[f]);
+ *   kind 2, the RollingPin (primitives.py:83-99; the Capsule's geometry and contact):  (dw, dth, dy) = a action_scale / substeps;
+ *     y_dir = qrot(rot[f], (0, -1, 0));  x_dir = cross((0, 1, 0), y_dir) dw 0.03, x_dir.y = dy;  pos[f+1] = clamp(pos[f] + x_dir);
+ *     rot[f+1] = qmul(w2quat((0, -dth, 0)), qmul(rot[f], w2quat((0, dw, 0)))) -- the position step depends on the rotation.
+ *   qmul (utils.py:19-27) is the Hamilton product, normalised: rot[f >= 1] is unit, rot[0] is used as given.  w2quat (utils.py:29-41)
+ *   is (cos(|w|/2), w/|w| sin(|w|/2)), and the identity when |w| <= 1e-9; on that arm the cotangent of w is DEFINED as 0 (taichi's reverse
+ *   mode would form 0 * inf there).  The contact at substep f is the Capsule's above with q = rot[f] (distance, normal, conj(q) / |q|) and
+ *   rot[f+1] in the collider velocity (primive_base.py:82-89); its adjoint also reaches rot[f] (through the inverse with its
+ *   normalisation, the local point and the normal's rotation back) and rot[f+1].  The reference asserts |q| > 0.9 (inv_trans); on the
+ *   device this is the CALLER'S duty: prim_rot is not checked.  Specification: tests/plb_rot_twin.py.
  * Parity for these entry points is UNPINNED: taichi is absent and the reference ships no recording of this path; the torch
  * restatements (oracle/twin/plb_twin_torch.py, tests/plb_prim_twin.py for the Capsule) are the specification the kernels are held to.
  * ------------------------------------------------------------------------------------------------ */
@@ -330,7 +344,7 @@ typedef struct {
   double dt;             /* 0.5e-4 / (quality * 0.5)                  :21 */
   double gravity[3];     /* SIMULATOR.gravity (the kernel applies x30, :205) */
   double ground_friction;
-  int n_primitives;      /* 1 or 2 primitives (Spheres unless prim_kind says otherwise); only primitive 0 is actuated (3 action dims) */
+  int n_primitives;      /* 1 or 2 primitives (Spheres unless prim_kind says otherwise); only primitive 0 is actuated (3 action dims, or action_dim) */
   double radius[2];
   double lower_bound[3], upper_bound[3];   /* primitive xyz_limit */
   int grid_ckpt_cells;   /* 0: ud_plb_step_bwd runs p2g again for every substep (substep_grad recomputes the whole substep,
@@ -355,13 +369,20 @@ typedef struct {
   int sort_every;        /* the handle orders each env's particles by grid cell internally (invisible at this boundary) on the first
                             call and every sort_every-th forward call after it; 0 = 8; negative = never */
   /* Everything below: zero = the handle of before these fields existed (sticky Spheres, action scale 1) */
-  int prim_kind[2];      /* 0 sticky Sphere, 1 Capsule (radius[i], capsule_h[i], prim_rot[i], prim_friction[i]); else UD_ERR_INVALID.  A handle
+  int prim_kind[2];      /* 0 sticky Sphere, 1 Capsule (radius[i], capsule_h[i], prim_rot[i], prim_friction[i]), 2 RollingPin (the Capsule's
+                            geometry, its own kinematics; needs rot_state and three action dimensions); else UD_ERR_INVALID.  A handle
                             with a Capsule runs the multi-kernel path (path = 0 picks it; path = 2: UD_ERR_UNSUPPORTED) */
   double capsule_h[2];   /* Capsule: length of the axis segment (along the primitive's y), >= 0; radius[i] > 0 */
   double prim_rot[2][4]; /* Capsule: constant orientation (w, x, y, z); all four zero = identity, else |q| > 0.9 as the reference asserts */
   double prim_friction[2];   /* Capsule: Coulomb friction of the contact (primitive cfg.friction) */
   double action_scale[3];    /* primitive 0: v = clip(action, -1, 1) * action_scale / substeps (set_velocity); all zero = (1, 1, 1).  Any
                                 other value: multi-kernel path, as with a Capsule */
+  int rot_state;             /* nonzero: every primitive's orientation is per-env state, passed through the *_rot entry points (prim_rot above is
+                                then unused by the kernels).  Primitive 0 must be kind 1 or 2, primitive 1 (unactuated, never moves) a sticky
+                                Sphere: anything else, and path = 2, UD_ERR_UNSUPPORTED */
+  int action_dim;            /* 0 or 3: three action dimensions.  6: (v, w) of the base class (set_velocity, primive_base.py:185-193); needs
+                                rot_state (UD_ERR_INVALID without) */
+  double action_scale_w[3];  /* action.scale[3:6]: w = clip(action[3:6], -1, 1) * action_scale_w / substeps; all zero = (1, 1, 1) */
 } ud_plb_conf;
 
 int ud_plb_create(const ud_plb_conf* conf, ud_plb** out);
@@ -384,6 +405,14 @@ int ud_plb_step_fwd(ud_plb* h, int B, const double* x, const double* v, const do
 /* ckpt (may be NULL = no backward): ud_plb_ckpt_bytes(h, B) bytes, caller-owned, opaque: every substep's particle state,
  * the primitive trajectory and the internal spatial order of this call, consumed by ud_plb_step_bwd. */
 size_t ud_plb_ckpt_bytes(const ud_plb* h, int B);
+/* The same on a rot_state handle (UD_ERR_INVALID on any other; ud_plb_step_fwd / _bwd / ud_plb_loss_* return UD_ERR_INVALID on a
+ * rot_state handle): prim_rot [B,n_primitives,4] (w, x, y, z; |q| > 0.9 is the caller's duty), action [B,action_dim], prim_rot_out
+ * [B,n_primitives,4].  The checkpoint (ud_plb_ckpt_bytes) also keeps the rotation trajectory.  Launches only: no allocation, no
+ * synchronisation. */
+int ud_plb_step_fwd_rot(ud_plb* h, int B, const double* x, const double* v, const double* C, const double* F,
+                        const double* prim_pos, const double* prim_rot, const double* softness, const double* action,
+                        const double* E, const double* nu, const double* yield_stress, double* x_out, double* v_out,
+                        double* C_out, double* F_out, double* prim_pos_out, double* prim_rot_out, void* ckpt, void* stream);
 
 /* Adjoint of one env.step.  g_x, g_v [B,N,3], g_C, g_F [B,N,3,3], g_prim_pos [B,n_primitives,3]: cotangents of the
  * step's outputs (any may be NULL = zero).  Outputs: cotangents of the inputs x, v, C, F (required), of prim_pos
@@ -394,6 +423,13 @@ int ud_plb_step_bwd(ud_plb* h, int B, const void* ckpt, const double* softness, 
                     const double* g_F, const double* g_prim_pos, double* g_x0, double* g_v0, double* g_C0, double* g_F0,
                     double* g_prim_pos0, double* g_action, double* g_E, double* g_nu, double* g_yield_stress,
                     double* g_ground_friction, void* stream);
+/* ... of ud_plb_step_fwd_rot: g_prim_rot [B,n_primitives,4] (in, may be NULL = zero), g_prim_rot0 [B,n_primitives,4] (out, may be
+ * NULL), g_action [B,action_dim]. */
+int ud_plb_step_bwd_rot(ud_plb* h, int B, const void* ckpt, const double* softness, const double* action, const double* E,
+                        const double* nu, const double* yield_stress, const double* g_x, const double* g_v, const double* g_C,
+                        const double* g_F, const double* g_prim_pos, const double* g_prim_rot, double* g_x0, double* g_v0,
+                        double* g_C0, double* g_F0, double* g_prim_pos0, double* g_prim_rot0, double* g_action, double* g_E,
+                        double* g_nu, double* g_yield_stress, double* g_ground_friction, void* stream);
 
 /* Loss of a particle state (engine/losses/loss.py): x [B,N,3], prim_pos [B,n_primitives,3], target_density and target_sdf
  * [n_grid^3] (shared by the envs), weights [3] = (contact, density, sdf) -- all device arrays.
@@ -407,6 +443,13 @@ int ud_plb_loss_fwd(ud_plb* h, int B, const double* x, const double* prim_pos, c
 int ud_plb_loss_bwd(ud_plb* h, int B, const double* x, const double* prim_pos, const double* target_density,
                     const double* target_sdf, const double* weights, int soft_contact, const double* g_loss, double* g_x,
                     double* g_prim_pos, void* stream);
+/* The same on a rot_state handle: the contact term takes the Capsule's distance in the primitive's current frame prim_rot
+ * [B,n_primitives,4]; g_prim_rot [B,n_primitives,4] (out, may be NULL). */
+int ud_plb_loss_fwd_rot(ud_plb* h, int B, const double* x, const double* prim_pos, const double* prim_rot, const double* target_density,
+                        const double* target_sdf, const double* weights, int soft_contact, double* loss, double* parts, void* stream);
+int ud_plb_loss_bwd_rot(ud_plb* h, int B, const double* x, const double* prim_pos, const double* prim_rot, const double* target_density,
+                        const double* target_sdf, const double* weights, int soft_contact, const double* g_loss, double* g_x,
+                        double* g_prim_pos, double* g_prim_rot, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Cloth-env arithmetic either side of the rollout (the reference jit-fuses it into step_diff; here one forward and

@@ -20,6 +20,7 @@ SYMBOLS = [
     "ud_cloth_rollout_fwd", "ud_cloth_rollout_bwd",
     "ud_mpm_create", "ud_mpm_destroy", "ud_mpm_ckpt_bytes", "ud_mpm_ckpt_cells", "ud_mpm_launch_plan", "ud_mpm_reset", "ud_mpm_step_fwd", "ud_mpm_step_bwd",
     "ud_plb_create", "ud_plb_destroy", "ud_plb_launch_plan", "ud_plb_poll_timeouts", "ud_plb_step_fwd", "ud_plb_ckpt_bytes", "ud_plb_step_bwd", "ud_plb_loss_fwd", "ud_plb_loss_bwd",
+    "ud_plb_step_fwd_rot", "ud_plb_step_bwd_rot", "ud_plb_loss_fwd_rot", "ud_plb_loss_bwd_rot",
     "ud_chamfer_fwd", "ud_chamfer_bwd", "ud_cloth_pnp_fwd", "ud_cloth_pnp_bwd", "ud_cloth_depth_fwd", "ud_cloth_depth_bwd",
     "ud_mpm_focus_fwd", "ud_mpm_focus_bwd", "ud_mpm_finish_fwd", "ud_mpm_finish_bwd",
 ]
@@ -52,7 +53,8 @@ class ud_plb_conf(C.Structure):
                 ("radius", C.c_double * 2), ("lower_bound", C.c_double * 3), ("upper_bound", C.c_double * 3),
                 ("grid_ckpt_cells", C.c_int), ("max_envs", C.c_int), ("path", C.c_int), ("lanes", C.c_int), ("sort_every", C.c_int),
                 ("prim_kind", C.c_int * 2), ("capsule_h", C.c_double * 2), ("prim_rot", (C.c_double * 4) * 2),
-                ("prim_friction", C.c_double * 2), ("action_scale", C.c_double * 3)]
+                ("prim_friction", C.c_double * 2), ("action_scale", C.c_double * 3),
+                ("rot_state", C.c_int), ("action_dim", C.c_int), ("action_scale_w", C.c_double * 3)]
 
 
 def build(force: bool = False) -> str:

@@ -162,7 +162,7 @@ __global__ void __launch_bounds__(256) plb_p2g(PlbArgs a) {
 }
 
 // grid_op (:200-232) over the touched cells.  GEN: the handle has a general primitive (plb_prim.h), fixed at create
-template <bool GEN>
+template <int GEN>   // 2: a rot_state handle, the substep's two quaternions per primitive read from the rotation trajectory
 __global__ void __launch_bounds__(256) plb_grid(PlbArgs a, PlbPrimArg<GEN> pr) {
   const int b = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x;
   const PlbConst& c = a.c;
@@ -184,6 +184,9 @@ __global__ void __launch_bounds__(256) plb_grid(PlbArgs a, PlbPrimArg<GEN> pr) {
     o[0] = cell[0]; o[1] = cell[1]; o[2] = cell[2]; o[3] = cell[3];
   }
   double vv[3];
+  if constexpr (GEN == 2) plb_grid_cell_any<GEN>(c, pr, lin, cell[0], cell + 1, a.w.pos + ((long)b * (c.S + 1) + a.f) * c.np * 3, a.softness + b * c.np, vv,
+                                                 pr.r.rot + ((long)b * (c.S + 1) + a.f) * c.np * 4);
+  else
   plb_grid_cell_any<GEN>(c, pr, lin, cell[0], cell + 1, a.w.pos + ((long)b * (c.S + 1) + a.f) * c.np * 3, a.softness + b * c.np, vv);
   cell[1] = vv[0]; cell[2] = vv[1]; cell[3] = vv[2];
 }
@@ -375,11 +378,59 @@ __global__ void __launch_bounds__(1024) plb_sort(PlbArgs a, const double* x, int
 
 // state into the history's slot 0 in the call's spatial order; block 0 of each env also runs the prologue (primitive positions of the whole
 // step, both list counts).  order: the handle's current spatial order (arena), copied to this call's perm (the checkpoint's, for the adjoint).
+// The kinematics of a rot_state handle for one env and primitive, the whole step, serially: Primitive.forward_kinematics (primive_base.py:117-121:
+// pos[f+1] = clamp(pos[f] + v), rot[f+1] = qmul(w2quat(w), rot[f]); v, w = clip(action) * scale / substeps for primitive 0, else 0) or, r.kin == 2 and
+// primitive 0, RollingPin.forward_kinematics (primitives.py:86-99), whose position step depends on the rotation.  rot[0] is used as given.
+__device__ __forceinline__ void plb_kinematics_rot(const PlbConst& c, const PlbRot& r, const PlbScale& sc, int b, int pi, const double* prim_pos,
+                                                   const double* prim_rot, const double* action, double* P, double* R) {
+  double pos[3], q[4], av[6] = {0, 0, 0, 0, 0, 0};
+#pragma unroll
+  for (int d = 0; d < 3; ++d) { pos[d] = prim_pos[((long)b * c.np + pi) * 3 + d]; P[pi * 3 + d] = pos[d]; }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) { q[k] = prim_rot[((long)b * c.np + pi) * 4 + k]; R[pi * 4 + k] = q[k]; }
+  if (pi == 0) {
+    for (int d = 0; d < r.adim; ++d) av[d] = fmin(fmax(action[(long)b * r.adim + d], -1.0), 1.0) * (d < 3 ? sc.s[d] : r.sw[d - 3]) / (double)c.S;
+  }
+  if (pi == 0 && r.kin == 2) {
+    const double dw = av[0], dth = av[1], dy = av[2];
+    const double wa[3] = {0.0, -dth, 0.0}, wb[3] = {0.0, dw, 0.0}, ey[3] = {0.0, -1.0, 0.0};
+    double A[4], Bq[4];
+    plb_w2quat(wa, A); plb_w2quat(wb, Bq);
+    for (int s = 0; s < c.S; ++s) {
+      double yd[3], inner[4], q1[4];
+      plb_qrot(q, ey, yd);
+      const double xd[3] = {yd[2] * dw * 0.03, dy, -yd[0] * dw * 0.03};      // cross((0, 1, 0), y_dir) * dw * 0.03, .y = dy
+      plb_qmul(q, Bq, inner);
+      plb_qmul(A, inner, q1);
+#pragma unroll
+      for (int d = 0; d < 3; ++d) { pos[d] = fmax(fmin(pos[d] + xd[d], c.hi[d]), c.lo[d]); P[((s + 1) * c.np + pi) * 3 + d] = pos[d]; }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) { q[k] = q1[k]; R[((s + 1) * c.np + pi) * 4 + k] = q[k]; }
+    }
+    return;
+  }
+  double dq[4];
+  plb_w2quat(av + 3, dq);
+  for (int s = 0; s < c.S; ++s) {
+    double q1[4];
+    plb_qmul(dq, q, q1);
+#pragma unroll
+    for (int d = 0; d < 3; ++d) { pos[d] = fmax(fmin(pos[d] + av[d], c.hi[d]), c.lo[d]); P[((s + 1) * c.np + pi) * 3 + d] = pos[d]; }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { q[k] = q1[k]; R[((s + 1) * c.np + pi) * 4 + k] = q[k]; }
+  }
+}
+
+template <bool ROT>   // a rot_state handle: one thread per primitive runs the serial kinematics above (prim_rot = rr.r.ext)
 __global__ void __launch_bounds__(256) plb_pack(PlbArgs a, const double* x, const double* v, const double* Cm, const double* F, const int* order,
-                                                const double* prim_pos, const double* action, PlbScale sc) {
+                                                const double* prim_pos, const double* action, PlbScale sc, PlbRotArg<ROT> rr) {
   const int b = blockIdx.y, p = blockIdx.x * blockDim.x + threadIdx.x;
   const PlbConst& c = a.c;
   if (blockIdx.x == 0) {
+    if constexpr (ROT) {      // one thread per primitive
+      if (threadIdx.x < c.np)
+        plb_kinematics_rot(c, rr.r, sc, b, threadIdx.x, prim_pos, rr.r.ext, action, a.w.pos + (long)b * (c.S + 1) * c.np * 3, rr.r.rot + (long)b * (c.S + 1) * c.np * 4);
+    } else
     if (threadIdx.x < c.np * 3) {   // pos[s+1] = clamp(pos[s] + v), v = clip(action) * scale / substeps for primitive 0 (set_velocity, primive_base.py:185-192); one thread per coordinate
       const int pi = threadIdx.x / 3, d = threadIdx.x % 3;
       double* P = a.w.pos + (long)b * (c.S + 1) * c.np * 3;
@@ -405,13 +456,18 @@ __global__ void __launch_bounds__(256) plb_pack(PlbArgs a, const double* x, cons
 }
 // end of a forward call in one launch: blocks [0, nb_unpack) write the last state back in the caller's order (+ the primitive positions),
 // the blocks behind them clear the last substep's cells
-__global__ void __launch_bounds__(256) plb_unpack_clear(PlbArgs a, int slot, double* x, double* v, double* Cm, double* F, double* prim_o, int nb_unpack) {
+template <bool ROT>   // a rot_state handle: also prim_rot_out (rr.r.ext)
+__global__ void __launch_bounds__(256) plb_unpack_clear(PlbArgs a, int slot, double* x, double* v, double* Cm, double* F, double* prim_o, int nb_unpack,
+                                                        PlbRotArg<ROT> rr) {
   const int b = blockIdx.y;
   const PlbConst& c = a.c;
   if ((int)blockIdx.x >= nb_unpack) { plb_clear_body(a, b, ((int)blockIdx.x - nb_unpack) * blockDim.x + threadIdx.x); return; }
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (blockIdx.x == 0 && threadIdx.x < c.np * 3)
     prim_o[(long)b * c.np * 3 + threadIdx.x] = a.w.pos[((long)b * (c.S + 1) + c.S) * c.np * 3 + threadIdx.x];   // copyframe(cur, 0)
+  if constexpr (ROT) {
+    if (blockIdx.x == 0 && threadIdx.x < c.np * 4) rr.r.ext[(long)b * c.np * 4 + threadIdx.x] = rr.r.rot[((long)b * (c.S + 1) + c.S) * c.np * 4 + threadIdx.x];
+  }
   if (p >= c.N) return;
   const double* h = plb_hist(a, b, slot);
   const int up = a.w.perm[(long)b * c.Np + p];
@@ -446,6 +502,7 @@ int plb_reserve(ud_plb* h, int B, bool multi_kernel) {
   const size_t o_gxs = mk ? take((size_t)B * 3 * c.Np * 8) : 0, o_gpos = mk ? take((size_t)B * (c.S + 1) * c.np * 3 * 8 + 64) : 0, o_gpar = mk ? take((size_t)B * 4 * 8) : 0;
   // both paths: the spatial order, the loss kernels' grid mass and partial sums
   const size_t o_order = take((size_t)B * c.Np * 4), o_gm = take((size_t)B * h->G * 8), o_lred = take((size_t)B * 16 * 8);
+  const size_t o_rot = h->rot_state ? take((size_t)B * (c.S + 1) * c.np * 4 * 8) : 0, o_grot = h->rot_state ? take((size_t)B * (c.S + 1) * c.np * 4 * 8) : 0;
   hipError_t e = hipMalloc(&h->arena, off);
   if (e != hipSuccess) { ud::set_error("ud_plb_create: hipMalloc(%zu MB) failed: %s", off >> 20, hipGetErrorString(e)); return UD_ERR_HIP; }
   e = hipMemset(h->arena, 0, off);
@@ -459,12 +516,13 @@ int plb_reserve(ud_plb* h, int B, bool multi_kernel) {
     h->w.gxs = (double*)(base + o_gxs); h->w.gpos = (double*)(base + o_gpos); h->w.gpar = (double*)(base + o_gpar);
   }
   h->order = (int*)(base + o_order); h->gm = (double*)(base + o_gm); h->lred = (double*)(base + o_lred);
+  if (h->rot_state) { h->rot.rot = (double*)(base + o_rot); h->rot.grot = (double*)(base + o_grot); }
   h->B = B; h->epoch = 1; h->sort_B = 0;
   return UD_OK;
 }
 
-// caller-owned checkpoint of one step call: hist[B][S+1][24][Np] | pos[B][S+1][np][3] | perm[B][Np] (int) | grid checkpoint
-PlbCkOff plb_ckpt_layout(const ud::PlbConst& c, int B) {
+// caller-owned checkpoint of one step call: hist[B][S+1][24][Np] | pos[B][S+1][np][3] | perm[B][Np] (int) | grid checkpoint | svd | rot[B][S+1][np][4]
+PlbCkOff plb_ckpt_layout(const ud::PlbConst& c, int B, bool rot) {
   PlbCkOff k{};
   size_t off = 0;
   auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
@@ -475,6 +533,7 @@ PlbCkOff plb_ckpt_layout(const ud::PlbConst& c, int B) {
   k.gck_lin = take((size_t)B * c.S * c.gck * 4);
   k.gck_val = take((size_t)B * c.S * c.gck * 32);
   k.svd = take((size_t)B * c.S * 21 * c.Np * 8);
+  k.rot = rot ? take((size_t)B * (c.S + 1) * c.np * 4 * 8) : 0;   // rot_state handles: the rotation trajectory, behind everything else
   k.total = off;
   return k;
 }
@@ -511,17 +570,37 @@ int ud_plb_create(const ud_plb_conf* conf, ud_plb** out) {
   const bool zero_scale = conf->action_scale[0] == 0 && conf->action_scale[1] == 0 && conf->action_scale[2] == 0;
   for (int d = 0; d < 3; ++d) h->ascale.s[d] = zero_scale ? 1.0 : conf->action_scale[d];
   const bool unit_scale = h->ascale.s[0] == 1.0 && h->ascale.s[1] == 1.0 && h->ascale.s[2] == 1.0;
+  // rotating primitives: orientation as per-env state, six action dimensions, the RollingPin's kinematics (all zero = none of it)
+  h->rot_state = conf->rot_state != 0;
+  if (!(conf->action_dim == 0 || conf->action_dim == 3 || conf->action_dim == 6)) {
+    ud::set_error("ud_plb_create: action_dim = %d (0 or 3: three action dimensions, 6: (v, w))", conf->action_dim); delete h; return UD_ERR_INVALID;
+  }
+  if (conf->action_dim == 6 && !h->rot_state) { ud::set_error("ud_plb_create: action_dim = 6 requires rot_state"); delete h; return UD_ERR_INVALID; }
+  h->rot.adim = conf->action_dim == 6 ? 6 : 3;
+  h->rot.kin = 1;
+  {
+    const double* sw = conf->action_scale_w;
+    const bool zero_w = sw[0] == 0 && sw[1] == 0 && sw[2] == 0;
+    for (int d = 0; d < 3; ++d) h->rot.sw[d] = zero_w ? 1.0 : sw[d];
+  }
   for (int pi = 0; pi < c.np; ++pi) {
     const int kind = conf->prim_kind[pi];
-    if (kind != 0 && kind != 1) { ud::set_error("ud_plb_create: prim_kind[%d] = %d (0 Sphere, 1 Capsule)", pi, kind); delete h; return UD_ERR_INVALID; }
+    if (kind != 0 && kind != 1 && kind != 2) { ud::set_error("ud_plb_create: prim_kind[%d] = %d (0 Sphere, 1 Capsule, 2 RollingPin)", pi, kind); delete h; return UD_ERR_INVALID; }
+    if (kind == 2 && !h->rot_state) { ud::set_error("ud_plb_create: prim_kind[%d] = 2 (RollingPin) requires rot_state", pi); delete h; return UD_ERR_INVALID; }
+    if (h->rot_state) {
+      if (pi == 0 && kind == 0) { ud::set_error("ud_plb_create: rot_state: primitive 0 must be a Capsule (1) or a RollingPin (2), not a sticky Sphere"); delete h; return UD_ERR_UNSUPPORTED; }
+      if (pi == 1 && kind != 0) { ud::set_error("ud_plb_create: rot_state: primitive 1 is unactuated and must be a sticky Sphere (prim_kind[1] = %d)", kind); delete h; return UD_ERR_UNSUPPORTED; }
+      if (kind == 2 && h->rot.adim != 3) { ud::set_error("ud_plb_create: the RollingPin takes three action dimensions (dw, dth, dy), action_dim = %d", conf->action_dim); delete h; return UD_ERR_UNSUPPORTED; }
+      if (kind == 2) h->rot.kin = 2;
+    }
     ud::PlbPrim& pr = h->prim;
-    pr.kind[pi] = kind; pr.h[pi] = conf->capsule_h[pi]; pr.mu[pi] = conf->prim_friction[pi];
+    pr.kind[pi] = kind == 2 ? 1 : kind; pr.h[pi] = conf->capsule_h[pi]; pr.mu[pi] = conf->prim_friction[pi];
     const double* q = conf->prim_rot[pi];
     const double n2 = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
     const bool ident = q[0] == 0 && q[1] == 0 && q[2] == 0 && q[3] == 0;
-    if (kind == 1) {
+    if (kind != 0) {
       h->gen = true;
-      if (!ident && !(std::sqrt(n2) > 0.9)) { ud::set_error("ud_plb_create: |prim_rot[%d]| = %g (the reference asserts > 0.9; all zero = identity)", pi, std::sqrt(n2)); delete h; return UD_ERR_INVALID; }
+      if (!h->rot_state && !ident && !(std::sqrt(n2) > 0.9)) { ud::set_error("ud_plb_create: |prim_rot[%d]| = %g (the reference asserts > 0.9; all zero = identity)", pi, std::sqrt(n2)); delete h; return UD_ERR_INVALID; }
       if (!(conf->capsule_h[pi] >= 0) || !(conf->radius[pi] > 0)) {
         ud::set_error("ud_plb_create: Capsule %d needs capsule_h >= 0 and radius > 0 (h = %g, r = %g)", pi, conf->capsule_h[pi], conf->radius[pi]); delete h; return UD_ERR_INVALID;
       }
@@ -536,7 +615,7 @@ int ud_plb_create(const ud_plb_conf* conf, ud_plb** out) {
   const bool mk_only = h->gen || !unit_scale;
   if (conf->path == 2 && mk_only) {
     ud::set_error("ud_plb_create: path = 2 (persistent) has no %s: such a handle runs the multi-kernel path (path = 0 or 1)",
-                  h->gen ? "Capsule primitive (prim_kind = 1)" : "action_scale other than (1, 1, 1)");
+                  h->rot_state ? "rotating primitives (rot_state)" : h->gen ? "Capsule primitive (prim_kind = 1)" : "action_scale other than (1, 1, 1)");
     delete h; return UD_ERR_UNSUPPORTED;
   }
   h->G = (long)c.n_grid * c.n_grid * c.n_grid;
@@ -569,7 +648,7 @@ void ud_plb_destroy(ud_plb* h) {
 
 size_t ud_plb_ckpt_bytes(const ud_plb* h, int B) {
   if (!h || B < 1) return 0;
-  return h->cl.per > 0 ? plb_cluster_ckpt_bytes(h, B) : plb_ckpt_layout(h->c, B).total;
+  return h->cl.per > 0 ? plb_cluster_ckpt_bytes(h, B) : plb_ckpt_layout(h->c, B, h->rot_state).total;
 }
 
 int ud_plb_launch_plan(const ud_plb* h, int B) {
@@ -596,16 +675,16 @@ int ud_plb_poll_timeouts(ud_plb* h, void* stream) {
   return n;
 }
 
-int ud_plb_step_fwd(ud_plb* h, int B, const double* x, const double* v, const double* C, const double* F,
-                    const double* prim_pos, const double* softness, const double* action, const double* E,
-                    const double* nu, const double* yield_stress, double* x_out, double* v_out, double* C_out,
-                    double* F_out, double* prim_pos_out, void* ckpt, void* stream) {
-  if (!h || !x || !v || !C || !F || !prim_pos || !softness || !action || !E || !nu || !yield_stress || !x_out || !v_out || !C_out ||
-      !F_out || !prim_pos_out) {
-    ud::set_error("ud_plb_step_fwd: null argument"); return UD_ERR_INVALID;
-  }
-  if (B < 1) { ud::set_error("ud_plb_step_fwd: B=%d", B); return UD_ERR_INVALID; }
-  if (B > h->B) { ud::set_error("ud_plb_step_fwd: B=%d exceeds the handle's max_envs=%d (arenas are sized at create)", B, h->B); return UD_ERR_INVALID; }
+}  // extern "C"
+
+// ud_plb_step_fwd (prim_rot == nullptr) and ud_plb_step_fwd_rot (a rot_state handle: prim_rot / prim_rot_out given)
+static int plb_step_fwd_impl(const char* who, ud_plb* h, int B, const double* x, const double* v, const double* C, const double* F,
+                             const double* prim_pos, const double* prim_rot, const double* softness, const double* action, const double* E,
+                             const double* nu, const double* yield_stress, double* x_out, double* v_out, double* C_out,
+                             double* F_out, double* prim_pos_out, double* prim_rot_out, void* ckpt, void* stream) {
+  if (B < 1) { ud::set_error("%s: B=%d", who, B); return UD_ERR_INVALID; }
+  if (B > h->B) { ud::set_error("%s: B=%d exceeds the handle's max_envs=%d (arenas are sized at create)", who, B, h->B); return UD_ERR_INVALID; }
+  const bool rot = prim_rot != nullptr;
   hipStream_t st = (hipStream_t)stream;
   // Spatial order: any permutation is valid, only its locality ages (a particle moves a fraction of a cell per step) -- computed on the
   // first call, when more envs arrive than it covers, and every sort_every-th call (conf; default 8) after that; kept in the handle and
@@ -626,9 +705,11 @@ int ud_plb_step_fwd(ud_plb* h, int B, const double* x, const double* v, const do
   a.c = h->c; a.w = h->w; a.B = h->B; a.Bcall = B; a.f = 0; a.epoch = 0; a.cap = h->cap; a.G = h->G;
   a.slots = 2; a.hs_in = 0; a.hs_out = 1; a.lb = 0; a.ls = 0; a.lprev = 1; a.lnext = 1; a.hs_out2 = 0; a.epoch2 = 0;
   a.ck_skip = 0; a.w.gck_cnt = nullptr; a.w.gck_lin = nullptr; a.w.gck_val = nullptr; a.w.svd = nullptr;
+  ud::PlbRot rr = h->rot;
   if (ckpt) {   // keep every substep's particle state, the primitive trajectory, the spatial order (and the touched grid cells) for ud_plb_step_bwd
     plb_bind_ckpt(a, h->c, B, ckpt);
     a.slots = h->c.S + 1;
+    if (rot) rr.rot = (double*)((char*)ckpt + plb_ckpt_layout(h->c, B, true).rot);
   }
   a.softness = softness; a.E = E; a.nu = nu; a.ys = yield_stress;
   const dim3 blk(256), gp((h->c.N + 255) / 256, B), gc((h->cap + 255) / 256, B);
@@ -636,7 +717,9 @@ int ud_plb_step_fwd(ud_plb* h, int B, const double* x, const double* v, const do
   // not fill the chip, 1 beyond; ud_plb_conf.lanes forces one mapping (how the tests reach all three at their sizes)
   const int lanes = h->lanes ? h->lanes : (((long)B * h->c.N <= 16000) ? 8 : (((long)B * h->c.N < 100000) ? 4 : 1));
   const dim3 gq((lanes * h->c.N + 255) / 256, B);
-  hipLaunchKernelGGL(ud::plb_pack, gp, blk, 0, st, a, x, v, C, F, sorted ? (const int*)h->order : (const int*)nullptr, prim_pos, action, h->ascale);
+  rr.ext = const_cast<double*>(prim_rot);
+  if (rot) hipLaunchKernelGGL(ud::plb_pack<true>, gp, blk, 0, st, a, x, v, C, F, sorted ? (const int*)h->order : (const int*)nullptr, prim_pos, action, h->ascale, ud::PlbRotArg<true>{rr});
+  else hipLaunchKernelGGL(ud::plb_pack<false>, gp, blk, 0, st, a, x, v, C, F, sorted ? (const int*)h->order : (const int*)nullptr, prim_pos, action, h->ascale, ud::PlbRotArg<false>{});
   // Per substep: plb_grid(f), then ONE particle launch: g2p(f) -> p2g(f + 1) (plb_g2p_p2g); p2g(0) opens the step, g2p(S - 1) closes it.
   const bool fused = true;
   const int S = h->c.S;
@@ -653,8 +736,9 @@ int ud_plb_step_fwd(ud_plb* h, int B, const double* x, const double* v, const do
   UD_PLB_LAUNCH(plb_p2g);
   for (int f = 0; f < S; ++f) {
     set(f);
-    if (h->gen) hipLaunchKernelGGL(ud::plb_grid<true>, gc, blk, 0, st, a, ud::PlbPrimArg<true>{h->prim});
-    else hipLaunchKernelGGL(ud::plb_grid<false>, gc, blk, 0, st, a, ud::PlbPrimArg<false>{});
+    if (rot) hipLaunchKernelGGL(ud::plb_grid<2>, gc, blk, 0, st, a, ud::PlbPrimArg<2>{h->prim, rr});
+    else if (h->gen) hipLaunchKernelGGL(ud::plb_grid<1>, gc, blk, 0, st, a, ud::PlbPrimArg<1>{h->prim});
+    else hipLaunchKernelGGL(ud::plb_grid<0>, gc, blk, 0, st, a, ud::PlbPrimArg<0>{});
     if (fused && f + 1 < S) {
       UD_PLB_LAUNCH(plb_g2p_p2g);
     } else {
@@ -667,10 +751,40 @@ int ud_plb_step_fwd(ud_plb* h, int B, const double* x, const double* v, const do
   }
   // back to the all-zero grid invariant: the cells of the last substep (its list is `lprev` of a substep S that never runs)
   set(S);
-  hipLaunchKernelGGL(ud::plb_unpack_clear, dim3(gp.x + gc.x, B), blk, 0, st, a, h->c.S % a.slots, x_out, v_out, C_out, F_out, prim_pos_out, (int)gp.x);
+  rr.ext = prim_rot_out;
+  if (rot) hipLaunchKernelGGL(ud::plb_unpack_clear<true>, dim3(gp.x + gc.x, B), blk, 0, st, a, h->c.S % a.slots, x_out, v_out, C_out, F_out, prim_pos_out, (int)gp.x, ud::PlbRotArg<true>{rr});
+  else hipLaunchKernelGGL(ud::plb_unpack_clear<false>, dim3(gp.x + gc.x, B), blk, 0, st, a, h->c.S % a.slots, x_out, v_out, C_out, F_out, prim_pos_out, (int)gp.x, ud::PlbRotArg<false>{});
   hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { ud::set_error("ud_plb_step_fwd: %s", hipGetErrorString(e)); return UD_ERR_HIP; }
+  if (e != hipSuccess) { ud::set_error("%s: %s", who, hipGetErrorString(e)); return UD_ERR_HIP; }
   return UD_OK;
+}
+
+extern "C" {
+
+int ud_plb_step_fwd(ud_plb* h, int B, const double* x, const double* v, const double* C, const double* F,
+                    const double* prim_pos, const double* softness, const double* action, const double* E,
+                    const double* nu, const double* yield_stress, double* x_out, double* v_out, double* C_out,
+                    double* F_out, double* prim_pos_out, void* ckpt, void* stream) {
+  if (!h || !x || !v || !C || !F || !prim_pos || !softness || !action || !E || !nu || !yield_stress || !x_out || !v_out || !C_out ||
+      !F_out || !prim_pos_out) {
+    ud::set_error("ud_plb_step_fwd: null argument"); return UD_ERR_INVALID;
+  }
+  if (h->rot_state) { ud::set_error("ud_plb_step_fwd: a rot_state handle steps through ud_plb_step_fwd_rot"); return UD_ERR_INVALID; }
+  return plb_step_fwd_impl("ud_plb_step_fwd", h, B, x, v, C, F, prim_pos, nullptr, softness, action, E, nu, yield_stress, x_out, v_out, C_out, F_out,
+                           prim_pos_out, nullptr, ckpt, stream);
+}
+
+int ud_plb_step_fwd_rot(ud_plb* h, int B, const double* x, const double* v, const double* C, const double* F,
+                        const double* prim_pos, const double* prim_rot, const double* softness, const double* action, const double* E,
+                        const double* nu, const double* yield_stress, double* x_out, double* v_out, double* C_out,
+                        double* F_out, double* prim_pos_out, double* prim_rot_out, void* ckpt, void* stream) {
+  if (!h || !x || !v || !C || !F || !prim_pos || !prim_rot || !softness || !action || !E || !nu || !yield_stress || !x_out || !v_out || !C_out ||
+      !F_out || !prim_pos_out || !prim_rot_out) {
+    ud::set_error("ud_plb_step_fwd_rot: null argument"); return UD_ERR_INVALID;
+  }
+  if (!h->rot_state) { ud::set_error("ud_plb_step_fwd_rot: the handle was not created with rot_state (use ud_plb_step_fwd)"); return UD_ERR_INVALID; }
+  return plb_step_fwd_impl("ud_plb_step_fwd_rot", h, B, x, v, C, F, prim_pos, prim_rot, softness, action, E, nu, yield_stress, x_out, v_out, C_out, F_out,
+                           prim_pos_out, prim_rot_out, ckpt, stream);
 }
 
 }  // extern "C"

@@ -25,7 +25,7 @@
 namespace ud {
 
 // ---- grid op, kept: v_out of every touched cell into buffer 1 (buffer 0 keeps (m, mv)) ---------------------------------
-template <bool GEN>   // the handle has a general primitive (plb_prim.h)
+template <int GEN>   // 1: the handle has a general primitive (plb_prim.h); 2: a rot_state handle, the substep's quaternions read from pr.r.rot
 __global__ void __launch_bounds__(256) plb_grid_keep(PlbArgs a, PlbPrimArg<GEN> pr) {
   const int b = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x;
   const PlbConst& c = a.c;
@@ -58,6 +58,9 @@ __global__ void __launch_bounds__(256) plb_grid_keep(PlbArgs a, PlbPrimArg<GEN> 
     cell = plb_buf(a, cur, b) + lin * 4;
   }
   double vv[3];
+  if constexpr (GEN == 2) plb_grid_cell_any<GEN>(c, pr, lin, cell[0], cell + 1, a.w.pos + ((long)b * (c.S + 1) + a.f) * c.np * 3, a.softness + b * c.np, vv,
+                                                 pr.r.rot + ((long)b * (c.S + 1) + a.f) * c.np * 4);
+  else
   plb_grid_cell_any<GEN>(c, pr, lin, cell[0], cell + 1, a.w.pos + ((long)b * (c.S + 1) + a.f) * c.np * 3, a.softness + b * c.np, vv);
   double* out = plb_vout(a, b) + lin * 4;   // never cleared: read only at cells this launch has just written
   out[0] = vv[0]; out[1] = vv[1]; out[2] = vv[2];
@@ -176,14 +179,16 @@ __global__ void __launch_bounds__(256) plb_g2p_adj(PlbArgs a, int gs_in) {
 }
 
 // ---- grid op adjoint (:200-232 in reverse), one touched cell per lane -------------------------------------------------
-template <bool GEN>
+template <int GEN>
 __global__ void __launch_bounds__(256) plb_grid_adj(PlbArgs a, PlbPrimArg<GEN> pr) {
+  constexpr bool ROT = GEN == 2;
   const int b = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x;
   const PlbConst& c = a.c;
   // per-env cotangents (sticky-sphere positions, ground friction): summed over the wave, one atomic per wave and word -- one per cell
   // put every cell near a sphere on the same few words of its env (cf. lg_grid_adj_tile, mpm_large.hip)
   double qs[2][3] = {{0, 0, 0}, {0, 0, 0}}, gfric = 0;
   [[maybe_unused]] double q0[2][3] = {{0, 0, 0}, {0, 0, 0}};   // GEN: what the cell sends to gpos[f], independent of qs
+  [[maybe_unused]] double gr0[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, gr1[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};   // ROT: ... to grot[f] / grot[f + 1]
   const bool inlist = t < min(a.w.count[a.lb * a.B + b], a.cap);
   const long lin = inlist ? a.w.list[((long)a.lb * a.B + b) * a.cap + t] : 0;
   const double* cell = plb_buf(a, a.lb, b) + lin * 4;
@@ -191,7 +196,9 @@ __global__ void __launch_bounds__(256) plb_grid_adj(PlbArgs a, PlbPrimArg<GEN> p
   if (inlist) {
     const double g[3] = {ga[0], ga[1], ga[2]};
     double gout[4];
-    if constexpr (GEN) plb_grid_cell_adj_gen(c, pr.p, lin, cell[0], cell + 1, g, a.w.pos + ((long)b * (c.S + 1) + a.f) * c.np * 3, a.softness + b * c.np, gout, q0, qs, gfric);
+    if constexpr (ROT) plb_grid_cell_adj_gen<true>(c, pr.p, lin, cell[0], cell + 1, g, a.w.pos + ((long)b * (c.S + 1) + a.f) * c.np * 3, a.softness + b * c.np, gout, q0, qs, gfric,
+                                                   pr.r.rot + ((long)b * (c.S + 1) + a.f) * c.np * 4, gr0, gr1);
+    else if constexpr (GEN == 1) plb_grid_cell_adj_gen(c, pr.p, lin, cell[0], cell + 1, g, a.w.pos + ((long)b * (c.S + 1) + a.f) * c.np * 3, a.softness + b * c.np, gout, q0, qs, gfric);
     else plb_grid_cell_adj(c, lin, cell[0], cell + 1, g, a.w.pos + ((long)b * (c.S + 1) + a.f) * c.np * 3, a.softness + b * c.np, gout, qs, gfric);
     ga[0] = gout[0]; ga[1] = gout[1]; ga[2] = gout[2]; ga[3] = gout[3];
   }
@@ -200,7 +207,19 @@ __global__ void __launch_bounds__(256) plb_grid_adj(PlbArgs a, PlbPrimArg<GEN> p
 #pragma unroll
   for (int pi = 0; pi < 2; ++pi) {
     if (pi >= c.np) break;
-    if constexpr (GEN) {
+    if constexpr (ROT) {      // the rotation cotangents, reduced as q0 / qs are: a wave sum behind a wave-uniform test, one atomic per wave and word
+      if (__any(gr0[pi][0] != 0.0 || gr0[pi][1] != 0.0 || gr0[pi][2] != 0.0 || gr0[pi][3] != 0.0 || gr1[pi][0] != 0.0 || gr1[pi][1] != 0.0 ||
+                gr1[pi][2] != 0.0 || gr1[pi][3] != 0.0)) {
+        double* grot = pr.r.grot + (((long)b * (c.S + 1) + a.f) * c.np + pi) * 4;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const double s0 = plb_wave_sum(gr0[pi][k]), s1 = plb_wave_sum(gr1[pi][k]);
+          if (lead && s0 != 0.0) atomicAdd(grot + k, s0);
+          if (lead && s1 != 0.0) atomicAdd(grot + c.np * 4 + k, s1);
+        }
+      }
+    }
+    if constexpr (GEN != 0) {
       if (!__any(qs[pi][0] != 0.0 || qs[pi][1] != 0.0 || qs[pi][2] != 0.0 || q0[pi][0] != 0.0 || q0[pi][1] != 0.0 || q0[pi][2] != 0.0)) continue;
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
@@ -330,10 +349,16 @@ __global__ void plb_adj_reset_counts(PlbArgs a) {
 }
 
 // cotangent of the step outputs -> gstate slot (in the spatial order of the checkpoint); zero the accumulators
-__global__ void __launch_bounds__(256) plb_adj_pack(PlbArgs a, int slot, const double* gx, const double* gv, const double* gC, const double* gF, const double* gpp) {
+template <bool ROT>   // a rot_state handle: also the rotation cotangents (rr.r.grot; g_prim_rot = rr.r.ext, may be null)
+__global__ void __launch_bounds__(256) plb_adj_pack(PlbArgs a, int slot, const double* gx, const double* gv, const double* gC, const double* gF, const double* gpp,
+                                                    PlbRotArg<ROT> rr) {
   const int b = blockIdx.y, p = blockIdx.x * blockDim.x + threadIdx.x;
   const PlbConst& c = a.c;
   if (blockIdx.x == 0) {
+    if constexpr (ROT) {      // the rotation cotangents: grot[S] seeded from g_prim_rot
+      for (int e = threadIdx.x; e < (c.S + 1) * c.np * 4; e += blockDim.x)
+        rr.r.grot[(long)b * (c.S + 1) * c.np * 4 + e] = (rr.r.ext && e >= c.S * c.np * 4) ? rr.r.ext[(long)b * c.np * 4 + e - c.S * c.np * 4] : 0.0;
+    }
     for (int e = threadIdx.x; e < (c.S + 1) * c.np * 3; e += blockDim.x)
       a.w.gpos[(long)b * (c.S + 1) * c.np * 3 + e] = (gpp && e >= c.S * c.np * 3) ? gpp[(long)b * c.np * 3 + e - c.S * c.np * 3] : 0.0;
     if (threadIdx.x < 4) a.w.gpar[b * 4 + threadIdx.x] = 0.0;
@@ -389,6 +414,90 @@ __global__ void plb_adj_epilogue(PlbArgs a, PlbScale sc, const double* action, d
   if (g_fric) g_fric[b] = a.w.gpar[b * 4 + 3];
 }
 
+// The same for a rot_state handle, one thread per env: f = S - 1 ... 0 through the adjoint of plb_kinematics_rot (plb.hip) -- the clamp passes where it
+// is inactive, qmul with its normalisation, w2quat (its identity arm sends 0 to w), and for the RollingPin the position step's dependence on
+// rotation[f] -- from gpos / grot (the step's output cotangents plus what the grid-op adjoints added) to g_prim_pos0, g_prim_rot0, g_action [B,adim].
+__global__ void __launch_bounds__(64) plb_adj_epilogue_rot(PlbArgs a, PlbRot r, PlbScale sc, const double* action, double* g_prim_pos0, double* g_prim_rot0, double* g_action,
+                                     double* g_E, double* g_nu, double* g_ys, double* g_fric) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= a.Bcall) return;   // g_action, g_prim_rot0, ... are the caller's [Bcall] arrays
+  const PlbConst& c = a.c;
+  const double* P = a.w.pos + (long)b * (c.S + 1) * c.np * 3;
+  double* G = a.w.gpos + (long)b * (c.S + 1) * c.np * 3;
+  const double* R = r.rot + (long)b * (c.S + 1) * c.np * 4;
+  double* GR = r.grot + (long)b * (c.S + 1) * c.np * 4;
+  for (int pi = 0; pi < c.np; ++pi) {
+    double raw[6] = {0, 0, 0, 0, 0, 0}, av[6] = {0, 0, 0, 0, 0, 0}, gav[6] = {0, 0, 0, 0, 0, 0};
+    if (pi == 0) {
+      for (int d = 0; d < r.adim; ++d) {
+        raw[d] = action[(long)b * r.adim + d];
+        av[d] = fmin(fmax(raw[d], -1.0), 1.0) * (d < 3 ? sc.s[d] : r.sw[d - 3]) / (double)c.S;
+      }
+    }
+    if (pi == 0 && r.kin == 2) {
+      const double dw = av[0], dth = av[1], dy = av[2];
+      const double wa[3] = {0.0, -dth, 0.0}, wb[3] = {0.0, dw, 0.0}, ey[3] = {0.0, -1.0, 0.0};
+      double A[4], Bq[4], gA[4] = {0, 0, 0, 0}, gB[4] = {0, 0, 0, 0};
+      plb_w2quat(wa, A); plb_w2quat(wb, Bq);
+      for (int s = c.S - 1; s >= 0; --s) {
+        const double* q = R + (s * c.np + pi) * 4;
+        double inner[4], ginner[4] = {0, 0, 0, 0}, gq[4] = {0, 0, 0, 0}, yd[3];
+        plb_qmul(q, Bq, inner);
+        plb_qmul_adj(A, inner, GR + ((s + 1) * c.np + pi) * 4, gA, ginner);
+        plb_qmul_adj(q, Bq, ginner, gq, gB);
+        plb_qrot(q, ey, yd);
+        const double xd[3] = {yd[2] * dw * 0.03, dy, -yd[0] * dw * 0.03};
+        double g[3];
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+          const double un = P[(s * c.np + pi) * 3 + d] + xd[d];
+          g[d] = (un >= c.lo[d] && un <= c.hi[d]) ? G[((s + 1) * c.np + pi) * 3 + d] : 0.0;
+          G[(s * c.np + pi) * 3 + d] += g[d];
+        }
+        gav[2] += g[1];
+        gav[0] += 0.03 * (g[0] * yd[2] - g[2] * yd[0]);
+        const double gy[3] = {-g[2] * dw * 0.03, 0.0, g[0] * dw * 0.03};
+        double gqy[4];
+        plb_qrot_adj_rot(q, ey, gy, gqy);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) GR[(s * c.np + pi) * 4 + k] += gq[k] + gqy[k];
+      }
+      double gwa[3], gwb[3];
+      plb_w2quat_adj(wa, gA, gwa); plb_w2quat_adj(wb, gB, gwb);
+      gav[1] = -gwa[1];
+      gav[0] += gwb[1];
+    } else {
+      double dq[4], gdq[4] = {0, 0, 0, 0};
+      plb_w2quat(av + 3, dq);
+      for (int s = c.S - 1; s >= 0; --s) {
+        double gq[4] = {0, 0, 0, 0};
+        plb_qmul_adj(dq, R + (s * c.np + pi) * 4, GR + ((s + 1) * c.np + pi) * 4, gdq, gq);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) GR[(s * c.np + pi) * 4 + k] += gq[k];
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+          const double un = P[(s * c.np + pi) * 3 + d] + av[d];
+          const double g = (un >= c.lo[d] && un <= c.hi[d]) ? G[((s + 1) * c.np + pi) * 3 + d] : 0.0;
+          G[(s * c.np + pi) * 3 + d] += g;
+          gav[d] += g;
+        }
+      }
+      plb_w2quat_adj(av + 3, gdq, gav + 3);
+    }
+    for (int d = 0; d < 3; ++d)
+      if (g_prim_pos0) g_prim_pos0[((long)b * c.np + pi) * 3 + d] = G[pi * 3 + d];
+    for (int k = 0; k < 4; ++k)
+      if (g_prim_rot0) g_prim_rot0[((long)b * c.np + pi) * 4 + k] = GR[pi * 4 + k];
+    if (pi == 0 && g_action)
+      for (int d = 0; d < r.adim; ++d)
+        g_action[(long)b * r.adim + d] = (raw[d] >= -1.0 && raw[d] <= 1.0) ? gav[d] * (d < 3 ? sc.s[d] : r.sw[d - 3]) / (double)c.S : 0.0;
+  }
+  if (g_E) g_E[b] = a.w.gpar[b * 4];
+  if (g_nu) g_nu[b] = a.w.gpar[b * 4 + 1];
+  if (g_ys) g_ys[b] = a.w.gpar[b * 4 + 2];
+  if (g_fric) g_fric[b] = a.w.gpar[b * 4 + 3];
+}
+
 // ---- losses (engine/losses/loss.py) -----------------------------------------------------------------------------------
 // grid mass of the particles (compute_grid_m_kernel): dense [B][G], zeroed by the caller
 __global__ void __launch_bounds__(256) plb_loss_mass(PlbConst c, long G, const double* x, double* gm) {
@@ -435,10 +544,33 @@ __global__ void __launch_bounds__(256) plb_loss_grid(long G, const double* gm, c
 // hard :120-124: a minimum, taken through the ordered-integer view of the non-negative double (lred[b][8 + pi], preset to +inf)
 // distance of a particle to primitive pi (before the max with 0): the sphere's, or on a GEN handle the Capsule's (plb_prim.h); its gradient in x is
 // grad / den (the sphere's is left as the quotient the callers have always formed: d / len)
-template <bool GEN>
-__device__ __forceinline__ double plb_loss_dist(const PlbConst& c, const PlbPrimArg<GEN>& pr, int pi, const double* xp, const double* pp, double* grad, double* den) {
+// ROT (a rot_state handle): the Capsule's distance in the frame of q, this env's current rotation of the primitive; gq (with grad; may be null):
+// the gradient of the distance in q, through the inverse with its normalisation
+template <int GEN>
+__device__ __forceinline__ double plb_loss_dist(const PlbConst& c, const PlbPrimArg<GEN>& pr, int pi, const double* xp, const double* pp, double* grad, double* den,
+                                                const double* q = nullptr, double* gq = nullptr) {
   const double d[3] = {xp[0] - pp[0], xp[1] - pp[1], xp[2] - pp[2]};
-  if constexpr (GEN) {
+  if constexpr (GEN == 2) {
+    if (pr.p.kind[pi] == 1) {
+      double qi[4], pl[3], p[3], pass_y;
+      plb_qinv(q, qi);
+      const double len = plb_capsule_local<true>(pr.p, pi, d, pl, p, pass_y, qi);
+      if (grad) {
+        const double zero[3] = {0, 0, 0};
+        double g[3];
+        plb_capsule_local_adj<true>(pr.p, pi, p, len, pass_y, 1.0, zero, zero, grad, qi, g);
+        *den = 1.0;
+        if (gq) {
+          double gqi[4];
+          plb_qrot_adj_rot(qi, d, g, gqi);
+          gq[0] = 0.0; gq[1] = 0.0; gq[2] = 0.0; gq[3] = 0.0;
+          plb_qinv_adj(q, qi, gqi, gq);
+        }
+      }
+      return len - c.radius[pi];
+    }
+  } else
+  if constexpr (GEN == 1) {
     if (pr.p.kind[pi] == 1) {
       double pl[3], p[3], pass_y;
       const double len = plb_capsule_local(pr.p, pi, d, pl, p, pass_y);
@@ -455,7 +587,7 @@ __device__ __forceinline__ double plb_loss_dist(const PlbConst& c, const PlbPrim
   return len - c.radius[pi];
 }
 
-template <bool GEN>
+template <int GEN>   // 2: a rot_state handle, the primitive's current rotation per env in pr.r.rot [B][np][4]
 __global__ void __launch_bounds__(256) plb_loss_contact(PlbConst c, PlbPrimArg<GEN> pr, const double* x, const double* prim_pos, int soft, double* lred) {
   __shared__ double sh[4];
   const int b = blockIdx.y, p = blockIdx.x * blockDim.x + threadIdx.x;
@@ -464,7 +596,8 @@ __global__ void __launch_bounds__(256) plb_loss_contact(PlbConst c, PlbPrimArg<G
     if (p < c.N) {
       const double* xp = x + ((long)b * c.N + p) * 3;
       const double* pp = prim_pos + ((long)b * c.np + pi) * 3;
-      dij = fmax(plb_loss_dist<GEN>(c, pr, pi, xp, pp, nullptr, nullptr), 0.0);
+      if constexpr (GEN == 2) dij = fmax(plb_loss_dist<GEN>(c, pr, pi, xp, pp, nullptr, nullptr, pr.r.rot + ((long)b * c.np + pi) * 4), 0.0);
+      else dij = fmax(plb_loss_dist<GEN>(c, pr, pi, xp, pp, nullptr, nullptr), 0.0);
       sw = 1.0 / (1.0 + dij * dij * 10000.0);
     }
     if (soft) {
@@ -495,12 +628,20 @@ __global__ void plb_loss_finish(PlbConst c, int B, int soft, const double* wts, 
 }
 
 // loss adjoint: g_x and g_prim_pos.  Needs gm (grid mass) and lred (the forward's sums) of the same inputs.
-template <bool GEN>
+// ROT: every lane of a wave stays (a lane past the last particle repeats it and sends nothing), for the wave sums of the rotation cotangent
+template <int GEN>   // 2: prim_rot in pr.r.rot, g_prim_rot in pr.r.grot (may be null)
 __global__ void __launch_bounds__(256) plb_loss_bwd_kernel(PlbConst c, PlbPrimArg<GEN> pr, long G, int soft, const double* wts, const double* x, const double* prim_pos,
                                                           const double* td, const double* tsdf, const double* gm, const double* lred,
                                                           const double* g_loss, double* g_x, double* g_pp) {
-  const int b = blockIdx.y, p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= c.N) return;
+  constexpr bool ROT = GEN == 2;
+  [[maybe_unused]] const double* prim_rot = nullptr;
+  [[maybe_unused]] double* g_pr = nullptr;
+  if constexpr (ROT) { prim_rot = pr.r.rot; g_pr = pr.r.grot; }
+  const int b = blockIdx.y;
+  int p = blockIdx.x * blockDim.x + threadIdx.x;
+  bool live = true;
+  if constexpr (ROT) { live = p < c.N; p = min(p, c.N - 1); }
+  else { if (p >= c.N) return; }
   const double gl = g_loss[b];
   const double* xp = x + ((long)b * c.N + p) * 3;
   int base[3];
@@ -524,7 +665,10 @@ __global__ void __launch_bounds__(256) plb_loss_bwd_kernel(PlbConst c, PlbPrimAr
   for (int pi = 0; pi < c.np; ++pi) {
     const double* pp = prim_pos + ((long)b * c.np + pi) * 3;
     double dn[3], len;   // gradient of the distance in x: dn / len
-    const double raw = plb_loss_dist<GEN>(c, pr, pi, xp, pp, dn, &len);
+    [[maybe_unused]] double gq[4] = {0, 0, 0, 0}, gqs[4] = {0, 0, 0, 0};
+    double raw;
+    if constexpr (ROT) raw = plb_loss_dist<GEN>(c, pr, pi, xp, pp, dn, &len, prim_rot + ((long)b * c.np + pi) * 4, gq);
+    else raw = plb_loss_dist<GEN>(c, pr, pi, xp, pp, dn, &len);
     const double dij = fmax(raw, 0.0);
     double gd = 0;   // d loss / d dij for this particle
     if (soft) {
@@ -537,14 +681,29 @@ __global__ void __launch_bounds__(256) plb_loss_bwd_kernel(PlbConst c, PlbPrimAr
       const double md = r[8 + pi];
       gd = (dij == md) ? gl * wts[0] * 2 * md : 0.0;   // the minimum passes its cotangent to the argmin (ties: every one of them)
     }
-    if (raw > 0.0 && gd != 0.0) {
+    if (raw > 0.0 && gd != 0.0 && live) {
       const double q[3] = {gd * dn[0] / len, gd * dn[1] / len, gd * dn[2] / len};
 #pragma unroll
       for (int k = 0; k < 3; ++k) { gx[k] += q[k]; if (g_pp) atomicAdd(g_pp + ((long)b * c.np + pi) * 3 + k, -q[k]); }
+      if constexpr (ROT) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) gqs[k] = gd * gq[k];
+      }
+    }
+    if constexpr (ROT) {      // wave sum behind a wave-uniform test, one atomic per wave and word (as plb_grid_adj)
+      if (g_pr && pr.p.kind[pi] == 1 && __any(gqs[0] != 0.0 || gqs[1] != 0.0 || gqs[2] != 0.0 || gqs[3] != 0.0)) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const double sm = plb_wave_sum(gqs[k]);
+          if ((threadIdx.x & 63) == 0 && sm != 0.0) atomicAdd(g_pr + ((long)b * c.np + pi) * 4 + k, sm);
+        }
+      }
     }
   }
+  if (live) {
 #pragma unroll
-  for (int k = 0; k < 3; ++k) g_x[((long)b * c.N + p) * 3 + k] = gx[k];
+    for (int k = 0; k < 3; ++k) g_x[((long)b * c.N + p) * 3 + k] = gx[k];
+  }
 }
 
 }  // namespace ud
@@ -552,6 +711,65 @@ __global__ void __launch_bounds__(256) plb_loss_bwd_kernel(PlbConst c, PlbPrimAr
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
+// ud_plb_step_bwd (rot == false) and ud_plb_step_bwd_rot (a rot_state handle)
+static int plb_step_bwd_impl(const char* who, bool rot, ud_plb* h, int B, const void* ckpt, const double* softness, const double* action, const double* E, const double* nu,
+                             const double* yield_stress, const double* g_x, const double* g_v, const double* g_C, const double* g_F,
+                             const double* g_prim_pos, const double* g_prim_rot, double* g_x0, double* g_v0, double* g_C0, double* g_F0, double* g_prim_pos0,
+                             double* g_prim_rot0, double* g_action, double* g_E, double* g_nu, double* g_yield_stress, double* g_ground_friction, void* stream) {
+  if (B < 1) { ud::set_error("%s: B=%d", who, B); return UD_ERR_INVALID; }
+  if (B > h->B) { ud::set_error("%s: B=%d exceeds the handle's max_envs=%d", who, B, h->B); return UD_ERR_INVALID; }
+  hipStream_t st = (hipStream_t)stream;
+  if (h->cl.per > 0)
+    return plb_cluster_step_bwd(h, B, ckpt, softness, action, E, nu, yield_stress, g_x, g_v, g_C, g_F, g_prim_pos, g_x0, g_v0, g_C0, g_F0,
+                                g_prim_pos0, g_action, g_E, g_nu, g_yield_stress, g_ground_friction, st);
+  ud::PlbArgs a{};
+  a.c = h->c; a.w = h->w; a.B = h->B; a.Bcall = B; a.f = 0; a.epoch = 0; a.cap = h->cap; a.G = h->G;
+  a.softness = softness; a.E = E; a.nu = nu; a.ys = yield_stress;
+  plb_bind_ckpt(a, h->c, B, const_cast<void*>(ckpt));
+  ud::PlbRot rr = h->rot;
+  if (rot) rr.rot = (double*)((char*)const_cast<void*>(ckpt) + plb_ckpt_layout(h->c, B, true).rot);
+  a.slots = h->c.S + 1; a.lb = 0; a.ls = 0; a.lprev = 1; a.lnext = 1; a.hs_out2 = 0; a.epoch2 = 0;
+  a.ck_skip = h->c.gck > 0 ? 1 : 0;
+  const bool never_recompute = h->c.gck >= h->cap;          // every substep of every env is in the grid checkpoint: no recompute launch at all
+  const int S = h->c.S;
+  const dim3 blk(256), gp((h->c.N + 255) / 256, B), gc((h->cap + 255) / 256, B), gpa((h->c.N + 127) / 128, B);
+  const int lanes = h->lanes ? h->lanes : (((long)B * h->c.N <= 16000) ? 8 : (((long)B * h->c.N < 100000) ? 4 : 1));   // as the forward (plb.hip)
+  const dim3 gq((lanes * h->c.N + 255) / 256, B), gqa((lanes * h->c.N + 127) / 128, B);
+  hipLaunchKernelGGL(ud::plb_adj_reset_counts, dim3((B + 63) / 64), dim3(64), 0, st, a);
+  rr.ext = const_cast<double*>(g_prim_rot);
+  if (rot) hipLaunchKernelGGL(ud::plb_adj_pack<true>, gp, blk, 0, st, a, S & 1, g_x, g_v, g_C, g_F, g_prim_pos, ud::PlbRotArg<true>{rr});
+  else hipLaunchKernelGGL(ud::plb_adj_pack<false>, gp, blk, 0, st, a, S & 1, g_x, g_v, g_C, g_F, g_prim_pos, ud::PlbRotArg<false>{});
+  // Five launches per reverse substep.  List and (m, mv) buffer alternate with the substep like the forward's: plb_grid_keep retires
+  // the cells of substep f + 1 (their buffer and cotangent cells back to zero) beside its own work, plb_g2p_adj resets that list's
+  // count -- the separate clear and count-reset launches of every substep are gone; one clear after the loop for substep 0.
+  for (int f = S - 1; f >= 0; --f) {
+    a.f = f; a.epoch = h->epoch++; a.hs_in = f; a.hs_out = f + 1; a.lb = f & 1; a.ls = a.lb; a.lprev = a.lb ^ 1; a.lnext = a.lprev;
+    if (!never_recompute) ud::plb_launch_p2g(a, lanes, lanes > 1 ? gq : gp, st);   // recompute (m, mv) (rewrites F[f + 1] with the same values); envs with a checkpointed substep leave at once
+    if (rot) hipLaunchKernelGGL(ud::plb_grid_keep<2>, gc, blk, 0, st, a, ud::PlbPrimArg<2>{h->prim, rr});
+    else if (h->gen) hipLaunchKernelGGL(ud::plb_grid_keep<1>, gc, blk, 0, st, a, ud::PlbPrimArg<1>{h->prim});
+    else hipLaunchKernelGGL(ud::plb_grid_keep<0>, gc, blk, 0, st, a, ud::PlbPrimArg<0>{});
+    if (lanes == 8) hipLaunchKernelGGL(ud::plb_g2p_adj<8>, gq, blk, 0, st, a, (f + 1) & 1);
+    else if (lanes == 4) hipLaunchKernelGGL(ud::plb_g2p_adj<4>, gq, blk, 0, st, a, (f + 1) & 1);
+    else hipLaunchKernelGGL(ud::plb_g2p_adj<1>, gp, blk, 0, st, a, (f + 1) & 1);
+    if (rot) hipLaunchKernelGGL(ud::plb_grid_adj<2>, gc, blk, 0, st, a, ud::PlbPrimArg<2>{h->prim, rr});
+    else if (h->gen) hipLaunchKernelGGL(ud::plb_grid_adj<1>, gc, blk, 0, st, a, ud::PlbPrimArg<1>{h->prim});
+    else hipLaunchKernelGGL(ud::plb_grid_adj<0>, gc, blk, 0, st, a, ud::PlbPrimArg<0>{});
+    if (lanes == 8) hipLaunchKernelGGL(ud::plb_p2g_adj<8>, gqa, dim3(128), 0, st, a, (f + 1) & 1);
+    else if (lanes == 4) hipLaunchKernelGGL(ud::plb_p2g_adj<4>, gqa, dim3(128), 0, st, a, (f + 1) & 1);
+    else hipLaunchKernelGGL(ud::plb_p2g_adj<1>, gpa, dim3(128), 0, st, a, (f + 1) & 1);
+  }
+  a.lb = 0; a.ls = 0; a.lprev = 1; a.lnext = 1;
+  hipLaunchKernelGGL(ud::plb_adj_clear, gc, blk, 0, st, a);
+  hipLaunchKernelGGL(ud::plb_adj_reset_counts, dim3((B + 63) / 64), dim3(64), 0, st, a);
+  hipLaunchKernelGGL(ud::plb_adj_unpack, gp, blk, 0, st, a, 0, g_x0, g_v0, g_C0, g_F0);
+  if (rot) hipLaunchKernelGGL(ud::plb_adj_epilogue_rot, dim3((B + 63) / 64), dim3(64), 0, st, a, rr, h->ascale, action, g_prim_pos0, g_prim_rot0, g_action, g_E, g_nu,
+                              g_yield_stress, g_ground_friction);
+  else hipLaunchKernelGGL(ud::plb_adj_epilogue, dim3((B + 63) / 64), dim3(64), 0, st, a, h->ascale, action, g_prim_pos0, g_action, g_E, g_nu, g_yield_stress, g_ground_friction);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { ud::set_error("%s: %s", who, hipGetErrorString(e)); return UD_ERR_HIP; }
+  return UD_OK;
+}
+
 extern "C" {
 
 int ud_plb_step_bwd(ud_plb* h, int B, const void* ckpt, const double* softness, const double* action, const double* E, const double* nu,
@@ -561,53 +779,26 @@ int ud_plb_step_bwd(ud_plb* h, int B, const void* ckpt, const double* softness, 
   if (!h || !ckpt || !softness || !action || !E || !nu || !yield_stress || !g_x0 || !g_v0 || !g_C0 || !g_F0) {
     ud::set_error("ud_plb_step_bwd: null argument"); return UD_ERR_INVALID;
   }
-  if (B < 1) { ud::set_error("ud_plb_step_bwd: B=%d", B); return UD_ERR_INVALID; }
-  if (B > h->B) { ud::set_error("ud_plb_step_bwd: B=%d exceeds the handle's max_envs=%d", B, h->B); return UD_ERR_INVALID; }
-  hipStream_t st = (hipStream_t)stream;
-  if (h->cl.per > 0)
-    return plb_cluster_step_bwd(h, B, ckpt, softness, action, E, nu, yield_stress, g_x, g_v, g_C, g_F, g_prim_pos, g_x0, g_v0, g_C0, g_F0,
-                                g_prim_pos0, g_action, g_E, g_nu, g_yield_stress, g_ground_friction, st);
-  ud::PlbArgs a{};
-  a.c = h->c; a.w = h->w; a.B = h->B; a.Bcall = B; a.f = 0; a.epoch = 0; a.cap = h->cap; a.G = h->G;
-  a.softness = softness; a.E = E; a.nu = nu; a.ys = yield_stress;
-  plb_bind_ckpt(a, h->c, B, const_cast<void*>(ckpt));
-  a.slots = h->c.S + 1; a.lb = 0; a.ls = 0; a.lprev = 1; a.lnext = 1; a.hs_out2 = 0; a.epoch2 = 0;
-  a.ck_skip = h->c.gck > 0 ? 1 : 0;
-  const bool never_recompute = h->c.gck >= h->cap;          // every substep of every env is in the grid checkpoint: no recompute launch at all
-  const int S = h->c.S;
-  const dim3 blk(256), gp((h->c.N + 255) / 256, B), gc((h->cap + 255) / 256, B), gpa((h->c.N + 127) / 128, B);
-  const int lanes = h->lanes ? h->lanes : (((long)B * h->c.N <= 16000) ? 8 : (((long)B * h->c.N < 100000) ? 4 : 1));   // as the forward (plb.hip)
-  const dim3 gq((lanes * h->c.N + 255) / 256, B), gqa((lanes * h->c.N + 127) / 128, B);
-  hipLaunchKernelGGL(ud::plb_adj_reset_counts, dim3((B + 63) / 64), dim3(64), 0, st, a);
-  hipLaunchKernelGGL(ud::plb_adj_pack, gp, blk, 0, st, a, S & 1, g_x, g_v, g_C, g_F, g_prim_pos);
-  // Five launches per reverse substep.  List and (m, mv) buffer alternate with the substep like the forward's: plb_grid_keep retires
-  // the cells of substep f + 1 (their buffer and cotangent cells back to zero) beside its own work, plb_g2p_adj resets that list's
-  // count -- the separate clear and count-reset launches of every substep are gone; one clear after the loop for substep 0.
-  for (int f = S - 1; f >= 0; --f) {
-    a.f = f; a.epoch = h->epoch++; a.hs_in = f; a.hs_out = f + 1; a.lb = f & 1; a.ls = a.lb; a.lprev = a.lb ^ 1; a.lnext = a.lprev;
-    if (!never_recompute) ud::plb_launch_p2g(a, lanes, lanes > 1 ? gq : gp, st);   // recompute (m, mv) (rewrites F[f + 1] with the same values); envs with a checkpointed substep leave at once
-    if (h->gen) hipLaunchKernelGGL(ud::plb_grid_keep<true>, gc, blk, 0, st, a, ud::PlbPrimArg<true>{h->prim});
-    else hipLaunchKernelGGL(ud::plb_grid_keep<false>, gc, blk, 0, st, a, ud::PlbPrimArg<false>{});
-    if (lanes == 8) hipLaunchKernelGGL(ud::plb_g2p_adj<8>, gq, blk, 0, st, a, (f + 1) & 1);
-    else if (lanes == 4) hipLaunchKernelGGL(ud::plb_g2p_adj<4>, gq, blk, 0, st, a, (f + 1) & 1);
-    else hipLaunchKernelGGL(ud::plb_g2p_adj<1>, gp, blk, 0, st, a, (f + 1) & 1);
-    if (h->gen) hipLaunchKernelGGL(ud::plb_grid_adj<true>, gc, blk, 0, st, a, ud::PlbPrimArg<true>{h->prim});
-    else hipLaunchKernelGGL(ud::plb_grid_adj<false>, gc, blk, 0, st, a, ud::PlbPrimArg<false>{});
-    if (lanes == 8) hipLaunchKernelGGL(ud::plb_p2g_adj<8>, gqa, dim3(128), 0, st, a, (f + 1) & 1);
-    else if (lanes == 4) hipLaunchKernelGGL(ud::plb_p2g_adj<4>, gqa, dim3(128), 0, st, a, (f + 1) & 1);
-    else hipLaunchKernelGGL(ud::plb_p2g_adj<1>, gpa, dim3(128), 0, st, a, (f + 1) & 1);
-  }
-  a.lb = 0; a.ls = 0; a.lprev = 1; a.lnext = 1;
-  hipLaunchKernelGGL(ud::plb_adj_clear, gc, blk, 0, st, a);
-  hipLaunchKernelGGL(ud::plb_adj_reset_counts, dim3((B + 63) / 64), dim3(64), 0, st, a);
-  hipLaunchKernelGGL(ud::plb_adj_unpack, gp, blk, 0, st, a, 0, g_x0, g_v0, g_C0, g_F0);
-  hipLaunchKernelGGL(ud::plb_adj_epilogue, dim3((B + 63) / 64), dim3(64), 0, st, a, h->ascale, action, g_prim_pos0, g_action, g_E, g_nu, g_yield_stress, g_ground_friction);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { ud::set_error("ud_plb_step_bwd: %s", hipGetErrorString(e)); return UD_ERR_HIP; }
-  return UD_OK;
+  if (h->rot_state) { ud::set_error("ud_plb_step_bwd: a rot_state handle goes through ud_plb_step_bwd_rot"); return UD_ERR_INVALID; }
+  return plb_step_bwd_impl("ud_plb_step_bwd", false, h, B, ckpt, softness, action, E, nu, yield_stress, g_x, g_v, g_C, g_F, g_prim_pos, nullptr, g_x0, g_v0, g_C0,
+                           g_F0, g_prim_pos0, nullptr, g_action, g_E, g_nu, g_yield_stress, g_ground_friction, stream);
 }
 
-static int plb_loss_common(ud_plb* h, int B, const double* x, const double* prim_pos, const double* target_density, const double* target_sdf,
+int ud_plb_step_bwd_rot(ud_plb* h, int B, const void* ckpt, const double* softness, const double* action, const double* E, const double* nu,
+                        const double* yield_stress, const double* g_x, const double* g_v, const double* g_C, const double* g_F,
+                        const double* g_prim_pos, const double* g_prim_rot, double* g_x0, double* g_v0, double* g_C0, double* g_F0, double* g_prim_pos0,
+                        double* g_prim_rot0, double* g_action, double* g_E, double* g_nu, double* g_yield_stress, double* g_ground_friction, void* stream) {
+  if (!h || !ckpt || !softness || !action || !E || !nu || !yield_stress || !g_x0 || !g_v0 || !g_C0 || !g_F0) {
+    ud::set_error("ud_plb_step_bwd_rot: null argument"); return UD_ERR_INVALID;
+  }
+  if (!h->rot_state) { ud::set_error("ud_plb_step_bwd_rot: the handle was not created with rot_state (use ud_plb_step_bwd)"); return UD_ERR_INVALID; }
+  return plb_step_bwd_impl("ud_plb_step_bwd_rot", true, h, B, ckpt, softness, action, E, nu, yield_stress, g_x, g_v, g_C, g_F, g_prim_pos, g_prim_rot, g_x0, g_v0,
+                           g_C0, g_F0, g_prim_pos0, g_prim_rot0, g_action, g_E, g_nu, g_yield_stress, g_ground_friction, stream);
+}
+
+}  // extern "C"
+
+static int plb_loss_common(ud_plb* h, int B, const double* x, const double* prim_pos, const double* prim_rot, const double* target_density, const double* target_sdf,
                            const double* weights, int soft_contact, hipStream_t st) {
   if (B > h->B) { ud::set_error("ud_plb_loss: B=%d exceeds the handle's max_envs=%d", B, h->B); return UD_ERR_INVALID; }
   const ud::PlbConst& c = h->c;
@@ -619,39 +810,76 @@ static int plb_loss_common(ud_plb* h, int B, const double* x, const double* prim
   const int gb = (int)std::min<long>((h->G + 255) / 256, 1024);
   hipLaunchKernelGGL(ud::plb_loss_grid, dim3(gb, B), blk, 0, st, h->G, (const double*)h->gm, target_density, target_sdf, h->lred);
   if (c.np > 0) {
-    if (h->gen) hipLaunchKernelGGL(ud::plb_loss_contact<true>, gp, blk, 0, st, c, ud::PlbPrimArg<true>{h->prim}, x, prim_pos, soft_contact, h->lred);
-    else hipLaunchKernelGGL(ud::plb_loss_contact<false>, gp, blk, 0, st, c, ud::PlbPrimArg<false>{}, x, prim_pos, soft_contact, h->lred);
+    ud::PlbRot rr = h->rot;
+    rr.rot = const_cast<double*>(prim_rot); rr.grot = nullptr;
+    if (prim_rot) hipLaunchKernelGGL(ud::plb_loss_contact<2>, gp, blk, 0, st, c, ud::PlbPrimArg<2>{h->prim, rr}, x, prim_pos, soft_contact, h->lred);
+    else if (h->gen) hipLaunchKernelGGL(ud::plb_loss_contact<1>, gp, blk, 0, st, c, ud::PlbPrimArg<1>{h->prim}, x, prim_pos, soft_contact, h->lred);
+    else hipLaunchKernelGGL(ud::plb_loss_contact<0>, gp, blk, 0, st, c, ud::PlbPrimArg<0>{}, x, prim_pos, soft_contact, h->lred);
   }
   return UD_OK;
 }
 
-int ud_plb_loss_fwd(ud_plb* h, int B, const double* x, const double* prim_pos, const double* target_density, const double* target_sdf,
-                    const double* weights, int soft_contact, double* loss, double* parts, void* stream) {
-  if (!h || !x || !prim_pos || !target_density || !target_sdf || !weights || !loss) { ud::set_error("ud_plb_loss_fwd: null argument"); return UD_ERR_INVALID; }
+static int plb_loss_fwd_impl(const char* who, ud_plb* h, int B, const double* x, const double* prim_pos, const double* prim_rot, const double* target_density,
+                             const double* target_sdf, const double* weights, int soft_contact, double* loss, double* parts, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  int rc = plb_loss_common(h, B, x, prim_pos, target_density, target_sdf, weights, soft_contact, st);
+  int rc = plb_loss_common(h, B, x, prim_pos, prim_rot, target_density, target_sdf, weights, soft_contact, st);
   if (rc) return rc;
   hipLaunchKernelGGL(ud::plb_loss_finish, dim3((B + 63) / 64), dim3(64), 0, st, h->c, B, soft_contact, weights, (const double*)h->lred, loss, parts);
   hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { ud::set_error("ud_plb_loss_fwd: %s", hipGetErrorString(e)); return UD_ERR_HIP; }
+  if (e != hipSuccess) { ud::set_error("%s: %s", who, hipGetErrorString(e)); return UD_ERR_HIP; }
   return UD_OK;
+}
+
+static int plb_loss_bwd_impl(const char* who, ud_plb* h, int B, const double* x, const double* prim_pos, const double* prim_rot, const double* target_density,
+                             const double* target_sdf, const double* weights, int soft_contact, const double* g_loss, double* g_x, double* g_prim_pos,
+                             double* g_prim_rot, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  int rc = plb_loss_common(h, B, x, prim_pos, prim_rot, target_density, target_sdf, weights, soft_contact, st);   // recompute the grid mass and the sums
+  if (rc) return rc;
+  if (g_prim_pos) { if (hipMemsetAsync(g_prim_pos, 0, (size_t)B * h->c.np * 3 * 8, st) != hipSuccess) { ud::set_error("%s: memset failed", who); return UD_ERR_HIP; } }
+  if (g_prim_rot) { if (hipMemsetAsync(g_prim_rot, 0, (size_t)B * h->c.np * 4 * 8, st) != hipSuccess) { ud::set_error("%s: memset failed", who); return UD_ERR_HIP; } }
+  const dim3 blk(256), gp((h->c.N + 255) / 256, B);
+  ud::PlbRot rr = h->rot;
+  rr.rot = const_cast<double*>(prim_rot); rr.grot = g_prim_rot;
+  if (prim_rot) hipLaunchKernelGGL(ud::plb_loss_bwd_kernel<2>, gp, blk, 0, st, h->c, ud::PlbPrimArg<2>{h->prim, rr}, h->G, soft_contact, weights, x, prim_pos,
+                                   target_density, target_sdf, (const double*)h->gm, (const double*)h->lred, g_loss, g_x, g_prim_pos);
+  else if (h->gen) hipLaunchKernelGGL(ud::plb_loss_bwd_kernel<1>, gp, blk, 0, st, h->c, ud::PlbPrimArg<1>{h->prim}, h->G, soft_contact, weights, x, prim_pos,
+                                 target_density, target_sdf, (const double*)h->gm, (const double*)h->lred, g_loss, g_x, g_prim_pos);
+  else hipLaunchKernelGGL(ud::plb_loss_bwd_kernel<0>, gp, blk, 0, st, h->c, ud::PlbPrimArg<0>{}, h->G, soft_contact, weights, x, prim_pos,
+                          target_density, target_sdf, (const double*)h->gm, (const double*)h->lred, g_loss, g_x, g_prim_pos);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { ud::set_error("%s: %s", who, hipGetErrorString(e)); return UD_ERR_HIP; }
+  return UD_OK;
+}
+
+extern "C" {
+
+int ud_plb_loss_fwd(ud_plb* h, int B, const double* x, const double* prim_pos, const double* target_density, const double* target_sdf,
+                    const double* weights, int soft_contact, double* loss, double* parts, void* stream) {
+  if (!h || !x || !prim_pos || !target_density || !target_sdf || !weights || !loss) { ud::set_error("ud_plb_loss_fwd: null argument"); return UD_ERR_INVALID; }
+  if (h->rot_state) { ud::set_error("ud_plb_loss_fwd: a rot_state handle goes through ud_plb_loss_fwd_rot"); return UD_ERR_INVALID; }
+  return plb_loss_fwd_impl("ud_plb_loss_fwd", h, B, x, prim_pos, nullptr, target_density, target_sdf, weights, soft_contact, loss, parts, stream);
+}
+
+int ud_plb_loss_fwd_rot(ud_plb* h, int B, const double* x, const double* prim_pos, const double* prim_rot, const double* target_density, const double* target_sdf,
+                        const double* weights, int soft_contact, double* loss, double* parts, void* stream) {
+  if (!h || !x || !prim_pos || !prim_rot || !target_density || !target_sdf || !weights || !loss) { ud::set_error("ud_plb_loss_fwd_rot: null argument"); return UD_ERR_INVALID; }
+  if (!h->rot_state) { ud::set_error("ud_plb_loss_fwd_rot: the handle was not created with rot_state (use ud_plb_loss_fwd)"); return UD_ERR_INVALID; }
+  return plb_loss_fwd_impl("ud_plb_loss_fwd_rot", h, B, x, prim_pos, prim_rot, target_density, target_sdf, weights, soft_contact, loss, parts, stream);
 }
 
 int ud_plb_loss_bwd(ud_plb* h, int B, const double* x, const double* prim_pos, const double* target_density, const double* target_sdf,
                     const double* weights, int soft_contact, const double* g_loss, double* g_x, double* g_prim_pos, void* stream) {
   if (!h || !x || !prim_pos || !target_density || !target_sdf || !weights || !g_loss || !g_x) { ud::set_error("ud_plb_loss_bwd: null argument"); return UD_ERR_INVALID; }
-  hipStream_t st = (hipStream_t)stream;
-  int rc = plb_loss_common(h, B, x, prim_pos, target_density, target_sdf, weights, soft_contact, st);   // recompute the grid mass and the sums
-  if (rc) return rc;
-  if (g_prim_pos) { if (hipMemsetAsync(g_prim_pos, 0, (size_t)B * h->c.np * 3 * 8, st) != hipSuccess) { ud::set_error("ud_plb_loss_bwd: memset failed"); return UD_ERR_HIP; } }
-  const dim3 blk(256), gp((h->c.N + 255) / 256, B);
-  if (h->gen) hipLaunchKernelGGL(ud::plb_loss_bwd_kernel<true>, gp, blk, 0, st, h->c, ud::PlbPrimArg<true>{h->prim}, h->G, soft_contact, weights, x, prim_pos,
-                                 target_density, target_sdf, (const double*)h->gm, (const double*)h->lred, g_loss, g_x, g_prim_pos);
-  else hipLaunchKernelGGL(ud::plb_loss_bwd_kernel<false>, gp, blk, 0, st, h->c, ud::PlbPrimArg<false>{}, h->G, soft_contact, weights, x, prim_pos,
-                          target_density, target_sdf, (const double*)h->gm, (const double*)h->lred, g_loss, g_x, g_prim_pos);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { ud::set_error("ud_plb_loss_bwd: %s", hipGetErrorString(e)); return UD_ERR_HIP; }
-  return UD_OK;
+  if (h->rot_state) { ud::set_error("ud_plb_loss_bwd: a rot_state handle goes through ud_plb_loss_bwd_rot"); return UD_ERR_INVALID; }
+  return plb_loss_bwd_impl("ud_plb_loss_bwd", h, B, x, prim_pos, nullptr, target_density, target_sdf, weights, soft_contact, g_loss, g_x, g_prim_pos, nullptr, stream);
+}
+
+int ud_plb_loss_bwd_rot(ud_plb* h, int B, const double* x, const double* prim_pos, const double* prim_rot, const double* target_density, const double* target_sdf,
+                        const double* weights, int soft_contact, const double* g_loss, double* g_x, double* g_prim_pos, double* g_prim_rot, void* stream) {
+  if (!h || !x || !prim_pos || !prim_rot || !target_density || !target_sdf || !weights || !g_loss || !g_x) { ud::set_error("ud_plb_loss_bwd_rot: null argument"); return UD_ERR_INVALID; }
+  if (!h->rot_state) { ud::set_error("ud_plb_loss_bwd_rot: the handle was not created with rot_state (use ud_plb_loss_bwd)"); return UD_ERR_INVALID; }
+  return plb_loss_bwd_impl("ud_plb_loss_bwd_rot", h, B, x, prim_pos, prim_rot, target_density, target_sdf, weights, soft_contact, g_loss, g_x, g_prim_pos, g_prim_rot, stream);
 }
 
 }  // extern "C"

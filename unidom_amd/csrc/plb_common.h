@@ -164,8 +164,10 @@ struct PlbScale { double s[3]; };   // action scale of primitive 0 (set_velocity
 // The same for a handle with a general primitive (plb_prim.h): kind 1 collides as Primitive.collide does, kind 0 sticks as above.  A function
 // of its own, and plb_grid_cell left to the letter: the persistent kernels inline that one at the edge of their register budget, and a
 // Sphere-only handle runs exactly the code it always ran.
+// ROT (a rot_state handle): Q0 = the quaternions of the env's primitives at substep f, Q0 + np*4 at f + 1.
+template <bool ROT = false>
 __device__ __forceinline__ void plb_grid_cell_gen(const PlbConst& c, const PlbPrim& pr, long lin, double m, const double* mv, const double* P0, const double* soft,
-                                                  double* vv) {
+                                                  double* vv, const double* Q0 = nullptr) {
   vv[0] = 0.0; vv[1] = 0.0; vv[2] = 0.0;
   if (!(m > 1e-12)) return;
   const int n = c.n_grid;
@@ -175,7 +177,11 @@ __device__ __forceinline__ void plb_grid_cell_gen(const PlbConst& c, const PlbPr
   const double gp[3] = {I[0] * c.dx, I[1] * c.dx, I[2] * c.dx};
   const double* P1 = P0 + c.np * 3;
   for (int pi = 0; pi < c.np; ++pi) {
-    if (pr.kind[pi] == 1) { plb_collide(pr, pi, c.radius[pi], c.dt, gp, P0 + pi * 3, P1 + pi * 3, soft[pi], vv); continue; }
+    if (pr.kind[pi] == 1) {
+      if constexpr (ROT) plb_collide_rot(pr, pi, c.radius[pi], c.dt, gp, P0 + pi * 3, P1 + pi * 3, Q0 + pi * 4, Q0 + (c.np + pi) * 4, soft[pi], vv);
+      else plb_collide(pr, pi, c.radius[pi], c.dt, gp, P0 + pi * 3, P1 + pi * 3, soft[pi], vv);
+      continue;
+    }
     const double d0 = gp[0] - P0[pi * 3], d1 = gp[1] - P0[pi * 3 + 1], d2 = gp[2] - P0[pi * 3 + 2];
     const double dist = sqrt(d0 * d0 + d1 * d1 + d2 * d2 + 1e-14) - c.radius[pi];
     const double sf = soft[pi];
@@ -200,10 +206,11 @@ __device__ __forceinline__ void plb_grid_cell_gen(const PlbConst& c, const PlbPr
     if (I[d] > n - 3 && vv[d] > 0) vv[d] = 0;
   }
 }
-template <bool GEN>
+template <int GEN>   // 0: sticky Spheres only, 1: a general primitive, 2: a rot_state handle (Q0: the substep's quaternions, see plb_grid_cell_gen)
 __device__ __forceinline__ void plb_grid_cell_any(const PlbConst& c, const PlbPrimArg<GEN>& pr, long lin, double m, const double* mv, const double* P0,
-                                                  const double* soft, double* vv) {
-  if constexpr (GEN) plb_grid_cell_gen(c, pr.p, lin, m, mv, P0, soft, vv);
+                                                  const double* soft, double* vv, const double* Q0 = nullptr) {
+  if constexpr (GEN == 2) plb_grid_cell_gen<true>(c, pr.p, lin, m, mv, P0, soft, vv, Q0);
+  else if constexpr (GEN == 1) plb_grid_cell_gen(c, pr.p, lin, m, mv, P0, soft, vv);
   else plb_grid_cell(c, lin, m, mv, P0, soft, vv);
 }
 
@@ -237,12 +244,14 @@ struct ud_plb {
   bool gen = false;         // some primitive is not a sticky Sphere: the GEN = true kernels of the multi-kernel path (plb_prim.h)
   ud::PlbPrim prim{};
   ud::PlbScale ascale{{1.0, 1.0, 1.0}};
+  bool rot_state = false;   // every primitive's orientation is per-env state (the _rot entry points); rot: its arenas and kinematics
+  ud::PlbRot rot{};
   PlbCluster cl;
 };
 // every arena of the handle, once, at create (no allocation and no host synchronisation in any step call)
 int plb_reserve(ud_plb* h, int B, bool multi_kernel);
-struct PlbCkOff { size_t hist, pos, perm, gck_cnt, gck_lin, gck_val, svd, total; };
-PlbCkOff plb_ckpt_layout(const ud::PlbConst& c, int B);
+struct PlbCkOff { size_t hist, pos, perm, gck_cnt, gck_lin, gck_val, svd, total, rot; };
+PlbCkOff plb_ckpt_layout(const ud::PlbConst& c, int B, bool rot = false);
 void plb_bind_ckpt(ud::PlbArgs& a, const ud::PlbConst& c, int B, void* ckpt);
 // persistent path (plb_cluster.hip)
 int plb_cluster_plan(ud_plb* h, int max_envs);

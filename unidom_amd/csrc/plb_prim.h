@@ -1,7 +1,10 @@
 // Primitive contact of the PlasticineLab-style f64 MLS-MPM grid op beyond the sticky Sphere: the base class's model
 // (GenORM/policy/pbm/plb/engine/primitive/primive_base.py:57-115 -- signed distance in the primitive's frame, rotated analytic
 // normal, soft influence, Coulomb friction) for the Capsule (primitives.py:55-73), one cell against one primitive, and its
-// hand-derived adjoint.  f64, plain C++; the orientation is a handle constant (action.dim = 3: w = 0, rotation[f + 1] = rotation[f]).
+// hand-derived adjoint.  f64, plain C++.  The orientation is a handle constant (action.dim = 3: w = 0, rotation[f + 1] = rotation[f]) or, on a
+// rot_state handle, per-env state: every function below is a template on ROT -- false (the default) reads the handle's constants pr.q / pr.qi exactly
+// as before, true takes q_f, conj(q_f) / |q_f| and q_{f+1} as pointers (one geometry, two instantiations) and its adjoint also returns the cotangents
+// of q_f and q_{f+1}.
 // Differentiable in the primitive's positions P_f (through the local point: distance, normal, influence, collider velocity) and
 // P_{f+1} (collider velocity) and in the incoming cell velocity; the branches (active, flag) are held constant, the sub-gradients
 // of min / max / clamp at equality are torch's (the checker is torch.autograd through tests/plb_prim_twin.py).
@@ -10,17 +13,30 @@
 
 namespace ud {
 
-// per-primitive constants of a handle with a general primitive; kind 0 = sticky Sphere, 1 = Capsule
+// per-primitive constants of a handle with a general primitive; kind 0 = sticky Sphere, 1 = Capsule (the RollingPin's contact is the Capsule's: kind 1 here)
 struct PlbPrim {
   int kind[2];
   double h[2], mu[2];
   double q[2][4];    // rotation (w, x, y, z) as given: qrot(q, .) takes the primitive's frame to the world
   double qi[2][4];   // conj(q) / |q|: inv_trans (utils.py:43-47)
 };
-// What the kernels of a handle take beside PlbArgs: nothing on a Sphere-only handle (the kernels it runs are the GEN = false
+// What the kernels of a handle take beside PlbArgs: nothing on a Sphere-only handle (the kernels it runs are the GEN = 0
 // instantiations, which hold no general code at all), the constants above otherwise.  Chosen at create.
-template <bool GEN> struct PlbPrimArg {};
-template <> struct PlbPrimArg<true> { PlbPrim p; };
+// On a rot_state handle (GEN = 2) also the rotation trajectory of this step and its cotangent, and the kinematics of primitive 0.
+struct PlbRot {
+  double* rot;      // [B][S+1][np][4] (w, x, y, z): handle arena, or the caller's checkpoint; the loss kernels: the caller's prim_rot [B][np][4]
+  double* grot;     // [B][S+1][np][4] cotangent (adjoint only); the loss adjoint: the caller's g_prim_rot [B][np][4] (may be null)
+  double* ext;      // the caller's [B][np][4] array of this launch: prim_rot (pack), prim_rot_out (unpack), g_prim_rot (adjoint pack; may be null)
+  int kin;          // kinematics of primitive 0: 1 = Primitive.forward_kinematics, 2 = RollingPin's
+  int adim;         // action dimensions: 3 or 6
+  double sw[3];     // action.scale[3:6]
+};
+template <int GEN> struct PlbPrimArg {};
+template <> struct PlbPrimArg<1> { PlbPrim p; };
+template <> struct PlbPrimArg<2> { PlbPrim p; PlbRot r; };
+// the extra argument of the pack / unpack kernels: nothing, or the above
+template <bool ROT> struct PlbRotArg {};
+template <> struct PlbRotArg<true> { PlbRot r; };
 
 __device__ __forceinline__ void plb_cross(const double* a, const double* b, double* o) {
   o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0];
@@ -38,20 +54,100 @@ __device__ __forceinline__ void plb_qrot_t(const double* rot, const double* g, d
   plb_qrot(cj, g, o);
 }
 
+// adjoint of plb_qrot in its rotation argument: g = cotangent of qrot(rot, v) -> grot (w, x, y, z), assigned
+__device__ __forceinline__ void plb_qrot_adj_rot(const double* rot, const double* v, const double* g, double* grot) {
+  double a[3], vg[3], ag[3], gu[3], vgu[3];
+  plb_cross(rot + 1, v, a);
+  plb_cross(v, g, vg);
+  plb_cross(a, g, ag);
+  plb_cross(g, rot + 1, gu);
+  plb_cross(v, gu, vgu);
+  grot[0] = 2 * (g[0] * a[0] + g[1] * a[1] + g[2] * a[2]);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) grot[1 + k] = 2 * (rot[0] * vg[k] + ag[k] + vgu[k]);
+}
+// utils.py:19-27: the Hamilton product q r, normalised
+__device__ __forceinline__ void plb_qmul(const double* q, const double* r, double* o) {
+  const double w = r[0] * q[0] - r[1] * q[1] - r[2] * q[2] - r[3] * q[3];
+  const double x = r[0] * q[1] + r[1] * q[0] - r[2] * q[3] + r[3] * q[2];
+  const double y = r[0] * q[2] + r[1] * q[3] + r[2] * q[0] - r[3] * q[1];
+  const double z = r[0] * q[3] - r[1] * q[2] + r[2] * q[1] + r[3] * q[0];
+  const double n = sqrt(w * w + x * x + y * y + z * z);
+  o[0] = w / n; o[1] = x / n; o[2] = y / n; o[3] = z / n;
+}
+// its adjoint: o = plb_qmul(q, r) again, go its cotangent; gq / gr are ADDED to
+__device__ __forceinline__ void plb_qmul_adj(const double* q, const double* r, const double* go, double* gq, double* gr) {
+  const double w = r[0] * q[0] - r[1] * q[1] - r[2] * q[2] - r[3] * q[3];
+  const double x = r[0] * q[1] + r[1] * q[0] - r[2] * q[3] + r[3] * q[2];
+  const double y = r[0] * q[2] + r[1] * q[3] + r[2] * q[0] - r[3] * q[1];
+  const double z = r[0] * q[3] - r[1] * q[2] + r[2] * q[1] + r[3] * q[0];
+  const double n = sqrt(w * w + x * x + y * y + z * z);
+  const double o[4] = {w / n, x / n, y / n, z / n};
+  const double dot = go[0] * o[0] + go[1] * o[1] + go[2] * o[2] + go[3] * o[3];
+  const double gw = (go[0] - dot * o[0]) / n, gx = (go[1] - dot * o[1]) / n, gy = (go[2] - dot * o[2]) / n, gz = (go[3] - dot * o[3]) / n;
+  gq[0] += gw * r[0] + gx * r[1] + gy * r[2] + gz * r[3];
+  gq[1] += -gw * r[1] + gx * r[0] - gy * r[3] + gz * r[2];
+  gq[2] += -gw * r[2] + gx * r[3] + gy * r[0] - gz * r[1];
+  gq[3] += -gw * r[3] - gx * r[2] + gy * r[1] + gz * r[0];
+  gr[0] += gw * q[0] + gx * q[1] + gy * q[2] + gz * q[3];
+  gr[1] += -gw * q[1] + gx * q[0] + gy * q[3] - gz * q[2];
+  gr[2] += -gw * q[2] - gx * q[3] + gy * q[0] + gz * q[1];
+  gr[3] += -gw * q[3] + gx * q[2] - gy * q[1] + gz * q[0];
+}
+// utils.py:29-41: axis-angle -> quaternion; the identity when |w| <= 1e-9
+__device__ __forceinline__ void plb_w2quat(const double* w, double* o) {
+  const double n = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+  o[0] = 1.0; o[1] = 0.0; o[2] = 0.0; o[3] = 0.0;
+  if (n > 1e-9) {
+    const double s = sin(n / 2);
+    o[0] = cos(n / 2); o[1] = w[0] / n * s; o[2] = w[1] / n * s; o[3] = w[2] / n * s;
+  }
+}
+// its adjoint, assigned; on the identity arm the cotangent of w is DEFINED as 0 (taichi's reverse mode would form 0 * inf there)
+__device__ __forceinline__ void plb_w2quat_adj(const double* w, const double* go, double* gw) {
+  const double n = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+  gw[0] = 0.0; gw[1] = 0.0; gw[2] = 0.0;
+  if (n > 1e-9) {
+    const double s = sin(n / 2), c = cos(n / 2);
+    const double gs = (go[1] * w[0] + go[2] * w[1] + go[3] * w[2]) / n;      // v = (w / n) s
+    const double gn = gs * c / 2 - go[0] * s / 2 - (go[1] * w[0] + go[2] * w[1] + go[3] * w[2]) * s / (n * n);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) gw[k] = go[1 + k] * s / n + gn * w[k] / n;
+  }
+}
+// conj(q) / |q| (inv_trans, utils.py:43-47) and its adjoint (gq ADDED to)
+__device__ __forceinline__ void plb_qinv(const double* q, double* qi) {
+  const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+  qi[0] = q[0] / n; qi[1] = -q[1] / n; qi[2] = -q[2] / n; qi[3] = -q[3] / n;
+}
+__device__ __forceinline__ void plb_qinv_adj(const double* q, const double* qi, const double* gqi, double* gq) {
+  const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+  const double dot = gqi[0] * qi[0] + gqi[1] * qi[1] + gqi[2] * qi[2] + gqi[3] * qi[3];
+  gq[0] += (gqi[0] - dot * qi[0]) / n;
+#pragma unroll
+  for (int k = 1; k < 4; ++k) gq[k] -= (gqi[k] - dot * qi[k]) / n;
+}
+// the orientation a ROT = false instantiation reads (the handle's constant) or a ROT = true one is given
+template <bool ROT> __device__ __forceinline__ const double* plb_sel(const double* of_handle, const double* given) {
+  if constexpr (ROT) return given; else return of_handle;
+}
+
 // Capsule._sdf / _normal (primitives.py:61-73) behind inv_trans: d = point - position.  pl = the point in the primitive's frame, p = the vector
 // from the nearest point of the axis segment, len = sqrt(p.p + 1e-14) (primitives.py's length); the distance is len - r, the local normal p / len.
 // pass_y: 1 where p.y moves with pl.y (beyond the segment's ends), 0 alongside it.
-__device__ __forceinline__ double plb_capsule_local(const PlbPrim& pr, int pi, const double* d, double* pl, double* p, double& pass_y) {
-  plb_qrot(pr.qi[pi], d, pl);
+template <bool ROT = false>   // qi: conj(q_f) / |q_f| (ROT)
+__device__ __forceinline__ double plb_capsule_local(const PlbPrim& pr, int pi, const double* d, double* pl, double* p, double& pass_y, const double* qi = nullptr) {
+  plb_qrot(plb_sel<ROT>(pr.qi[pi], qi), d, pl);
   const double py = pl[1] + pr.h[pi] / 2;
   p[0] = pl[0]; p[2] = pl[2];
   p[1] = py - fmin(fmax(py, 0.0), pr.h[pi]);
   pass_y = (py >= 0.0 && py <= pr.h[pi]) ? 0.0 : 1.0;
   return sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2] + 1e-14);
 }
-// cotangents (glen of len, gnl of the local normal p / len, gpl of pl directly) -> cotangent of d
+// cotangents (glen of len, gnl of the local normal p / len, gpl of pl directly) -> cotangent of d; ROT: also gpl_all, the whole cotangent of pl
+template <bool ROT = false>
 __device__ __forceinline__ void plb_capsule_local_adj(const PlbPrim& pr, int pi, const double* p, double len, double pass_y, double glen, const double* gnl,
-                                                      const double* gpl, double* gd) {
+                                                      const double* gpl, double* gd, const double* qi = nullptr, double* gpl_all = nullptr) {
   const double il = 1.0 / len;
   const double gl = glen - (gnl[0] * p[0] + gnl[1] * p[1] + gnl[2] * p[2]) * il * il;
   double g[3];
@@ -60,7 +156,8 @@ __device__ __forceinline__ void plb_capsule_local_adj(const PlbPrim& pr, int pi,
   g[1] *= pass_y;
 #pragma unroll
   for (int k = 0; k < 3; ++k) g[k] += gpl[k];
-  plb_qrot_t(pr.qi[pi], g, gd);
+  plb_qrot_t(plb_sel<ROT>(pr.qi[pi], qi), g, gd);
+  if constexpr (ROT) { gpl_all[0] = g[0]; gpl_all[1] = g[1]; gpl_all[2] = g[2]; }
 }
 
 // everything Primitive.collide (primive_base.py:91-115) computes for one cell, kept for the adjoint
@@ -68,11 +165,14 @@ struct PlbCollide {
   bool active, flag;
   double pl[3], p[3], pass_y, len, dist, D[3], e, infl, cv[3], w[3], nc, mn, t[3], tn, arg, ts[3];
 };
-// gp: cell position, P0 / P1: the primitive's position at substeps f / f + 1, sf: softness, u: the cell velocity so far
+// gp: cell position, P0 / P1: the primitive's position at substeps f / f + 1, sf: softness, u: the cell velocity so far; ROT: q0 / qi / q1 =
+// rotation[f], conj / |.| of it, rotation[f + 1]
+template <bool ROT = false>
 __device__ __forceinline__ void plb_collide_eval(const PlbPrim& pr, int pi, double radius, double dt, const double* gp, const double* P0, const double* P1,
-                                                 double sf, const double* u, PlbCollide& k) {
+                                                 double sf, const double* u, PlbCollide& k, const double* q0 = nullptr, const double* qi = nullptr,
+                                                 const double* q1 = nullptr) {
   const double d[3] = {gp[0] - P0[0], gp[1] - P0[1], gp[2] - P0[2]};
-  k.len = plb_capsule_local(pr, pi, d, k.pl, k.p, k.pass_y);
+  k.len = plb_capsule_local<ROT>(pr, pi, d, k.pl, k.p, k.pass_y, qi);
   k.dist = k.len - radius;
   k.e = exp(-k.dist * sf);
   k.infl = fmin(k.e, 1.0);
@@ -80,9 +180,9 @@ __device__ __forceinline__ void plb_collide_eval(const PlbPrim& pr, int pi, doub
   k.flag = false;
   if (!k.active) return;
   const double nl[3] = {k.p[0] / k.len, k.p[1] / k.len, k.p[2] / k.len};
-  plb_qrot(pr.q[pi], nl, k.D);
+  plb_qrot(plb_sel<ROT>(pr.q[pi], q0), nl, k.D);
   double back[3];
-  plb_qrot(pr.q[pi], k.pl, back);                            // rotation[f + 1] = rotation[f]
+  plb_qrot(plb_sel<ROT>(pr.q[pi], q1), k.pl, back);          // constant orientation: rotation[f + 1] = rotation[f]
 #pragma unroll
   for (int i = 0; i < 3; ++i) { k.cv[i] = (back[i] + P1[i] - gp[i]) / dt; k.w[i] = u[i] - k.cv[i]; }
   k.nc = k.w[0] * k.D[0] + k.w[1] * k.D[1] + k.w[2] * k.D[2];
@@ -107,9 +207,29 @@ __device__ __forceinline__ bool plb_collide(const PlbPrim& pr, int pi, double ra
   for (int i = 0; i < 3; ++i) u[i] = k.cv[i] + k.w[i] * (1 - k.infl) + k.ts[i] * k.infl;
   return true;
 }
-// adjoint of an ACTIVE collide: G = cotangent of u_out (in), cotangent of u_in (out, may alias nothing of the inputs); g0 / g1 = cotangents of P_f / P_{f+1}
+// the same on a rot_state handle: q0 / q1 = rotation[f] / rotation[f + 1] of this env and primitive
+__device__ __forceinline__ void plb_collide_eval_rot(const PlbPrim& pr, int pi, double radius, double dt, const double* gp, const double* P0, const double* P1,
+                                                     const double* q0, const double* q1, double sf, const double* u, PlbCollide& k) {
+  double qi[4];
+  plb_qinv(q0, qi);
+  plb_collide_eval<true>(pr, pi, radius, dt, gp, P0, P1, sf, u, k, q0, qi, q1);
+}
+__device__ __forceinline__ bool plb_collide_rot(const PlbPrim& pr, int pi, double radius, double dt, const double* gp, const double* P0, const double* P1,
+                                                const double* q0, const double* q1, double sf, double* u) {
+  PlbCollide k;
+  plb_collide_eval_rot(pr, pi, radius, dt, gp, P0, P1, q0, q1, sf, u, k);
+  if (!k.active) return false;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) u[i] = k.cv[i] + k.w[i] * (1 - k.infl) + k.ts[i] * k.infl;
+  return true;
+}
+// adjoint of an ACTIVE collide: G = cotangent of u_out (in), cotangent of u_in (out, may alias nothing of the inputs); g0 / g1 = cotangents of P_f / P_{f+1}.
+// ROT: also gq0 / gq1 = cotangents of rotation[f] (through the normal's rotation back, the local point and the inverse with its normalisation) and of
+// rotation[f + 1] (through the collider velocity), assigned; d = cell - P_f.
+template <bool ROT = false>
 __device__ __forceinline__ void plb_collide_adj(const PlbPrim& pr, int pi, double dt, const PlbCollide& k, double sf, const double* G, double* gu, double* g0,
-                                                double* g1) {
+                                                double* g1, const double* q0 = nullptr, const double* qi = nullptr, const double* q1 = nullptr,
+                                                const double* d = nullptr, double* gq0 = nullptr, double* gq1 = nullptr) {
   double gcv[3], gw[3], gt[3], gD[3];
   double ginfl = 0, gnc = 0;
 #pragma unroll
@@ -142,11 +262,28 @@ __device__ __forceinline__ void plb_collide_adj(const PlbPrim& pr, int pi, doubl
   double gback[3], gpl[3], gnl[3], gd[3];
 #pragma unroll
   for (int i = 0; i < 3; ++i) { gback[i] = gcv[i] / dt; g1[i] = gback[i]; }
-  plb_qrot_t(pr.q[pi], gback, gpl);
-  plb_qrot_t(pr.q[pi], gD, gnl);
-  plb_capsule_local_adj(pr, pi, k.p, k.len, k.pass_y, glen, gnl, gpl, gd);
+  plb_qrot_t(plb_sel<ROT>(pr.q[pi], q1), gback, gpl);
+  plb_qrot_t(plb_sel<ROT>(pr.q[pi], q0), gD, gnl);
+  [[maybe_unused]] double gpl_all[3];
+  plb_capsule_local_adj<ROT>(pr, pi, k.p, k.len, k.pass_y, glen, gnl, gpl, gd, qi, gpl_all);
 #pragma unroll
   for (int i = 0; i < 3; ++i) g0[i] = -gd[i];                // d = g - P_f
+  if constexpr (ROT) {
+    const double nl[3] = {k.p[0] / k.len, k.p[1] / k.len, k.p[2] / k.len};
+    double gqi[4];
+    plb_qrot_adj_rot(q1, k.pl, gback, gq1);
+    plb_qrot_adj_rot(q0, nl, gD, gq0);
+    plb_qrot_adj_rot(qi, d, gpl_all, gqi);
+    plb_qinv_adj(q0, qi, gqi, gq0);
+  }
+}
+__device__ __forceinline__ void plb_collide_adj_rot(const PlbPrim& pr, int pi, double dt, const PlbCollide& k, double sf, const double* gp, const double* P0,
+                                                    const double* q0, const double* q1, const double* G, double* gu, double* g0, double* g1, double* gq0,
+                                                    double* gq1) {
+  double qi[4];
+  plb_qinv(q0, qi);
+  const double d[3] = {gp[0] - P0[0], gp[1] - P0[1], gp[2] - P0[2]};
+  plb_collide_adj<true>(pr, pi, dt, k, sf, G, gu, g0, g1, q0, qi, q1, d, gq0, gq1);
 }
 
 }  // namespace ud

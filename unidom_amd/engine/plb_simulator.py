@@ -14,7 +14,7 @@ get_parameter_grad) and the ground friction (optimize_ground_friction, :57-58; `
 from __future__ import annotations
 
 import ctypes as C
-from typing import NamedTuple
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -32,6 +32,7 @@ class PlbState(NamedTuple):
     E: torch.Tensor          # [B]
     nu: torch.Tensor         # [B]
     yield_stress: torch.Tensor  # [B]
+    prim_rot: Optional[torch.Tensor] = None   # [B,n_prim,4] (w, x, y, z): a rot_state simulator only
 
 
 class PlbConf:
@@ -59,6 +60,12 @@ class PlbConf:
     prim_rot = ((1.0, 0.0, 0.0, 0.0), (1.0, 0.0, 0.0, 0.0))
     prim_friction = (0.0, 0.0)
     action_scale = (1.0, 1.0, 1.0)
+    # rotating primitives (ud_plb_conf.rot_state): every primitive's orientation is per-env state (PlbState.prim_rot, reset to prim_rot) and
+    # turns once per substep; action_dim 6 = (v, w) of the base class, w scaled by action_scale_w; prim_kind 2 = RollingPin (three
+    # action dimensions (dw, dth, dy), its own kinematics)
+    rot_state = False
+    action_dim = 3
+    action_scale_w = (1.0, 1.0, 1.0)
     softness = 666.0         # Primitive cfg default, set_softness()
 
 
@@ -134,6 +141,77 @@ class _PlbStep(torch.autograd.Function):
         return None, ox, ov, oC, oF, op, None, oa, oE, onu, oys
 
 
+class _PlbStepRot(torch.autograd.Function):
+    """_PlbStep over ud_plb_step_fwd_rot / _bwd_rot: prim_rot [B,P,4] is a state tensor and a differentiable leaf, action [B,action_dim]."""
+    @staticmethod
+    def forward(ctx, sim, x, v, Cm, F, pp, pr, so, action, E, nu, ys):
+        L = _lib.lib()
+        B = x.shape[0]
+        x, v, Cm, F, pp, pr, so, action, E, nu, ys = map(_c, (x, v, Cm, F, pp, pr, so, action, E, nu, ys))
+        xo, vo, Co, Fo, po, ro = (torch.empty_like(t) for t in (x, v, Cm, F, pp, pr))
+        ckpt = None
+        if any(ctx.needs_input_grad):
+            ckpt = torch.empty((L.ud_plb_ckpt_bytes(sim._h, C.c_int(B)) // 8,), dtype=torch.float64, device=x.device)
+        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        ev = sim._prof_begin("fwd")
+        _lib.check(L.ud_plb_step_fwd_rot(sim._h, C.c_int(B), _p(x), _p(v), _p(Cm), _p(F), _p(pp), _p(pr), _p(so), _p(action), _p(E), _p(nu),
+                                         _p(ys), _p(xo), _p(vo), _p(Co), _p(Fo), _p(po), _p(ro), _p(ckpt), stream), "ud_plb_step_fwd_rot")
+        sim._prof_end(ev)
+        ctx.sim, ctx.B = sim, B
+        ctx.save_for_backward(ckpt, so, action, E, nu, ys)
+        return xo, vo, Co, Fo, po, ro
+
+    @staticmethod
+    def backward(ctx, gx, gv, gC, gF, gpp, gpr):
+        L = _lib.lib()
+        sim, B = ctx.sim, ctx.B
+        ckpt, so, action, E, nu, ys = ctx.saved_tensors
+        if ckpt is None:
+            raise _lib.UnidomError("PLB step backward without a checkpoint (forward ran under no_grad)")
+        N, P, dev = sim.n_particles, sim.n_primitive, so.device
+        g = lambda t: None if t is None else _c(t)
+        gx, gv, gC, gF, gpp, gpr = map(g, (gx, gv, gC, gF, gpp, gpr))
+        mk = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+        ox, ov, oC, oF, op, orot, oa = mk(B, N, 3), mk(B, N, 3), mk(B, N, 3, 3), mk(B, N, 3, 3), mk(B, P, 3), mk(B, P, 4), mk(B, sim.action_dim)
+        oE, onu, oys, ofr = mk(B), mk(B), mk(B), mk(B)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        ev = sim._prof_begin("bwd")
+        _lib.check(L.ud_plb_step_bwd_rot(sim._h, C.c_int(B), _p(ckpt), _p(so), _p(action), _p(E), _p(nu), _p(ys), _p(gx), _p(gv), _p(gC),
+                                         _p(gF), _p(gpp), _p(gpr), _p(ox), _p(ov), _p(oC), _p(oF), _p(op), _p(orot), _p(oa), _p(oE), _p(onu),
+                                         _p(oys), _p(ofr), stream), "ud_plb_step_bwd_rot")
+        sim._prof_end(ev)
+        sim.ground_friction_grad = ofr if sim.ground_friction_grad is None else sim.ground_friction_grad + ofr
+        return None, ox, ov, oC, oF, op, orot, None, oa, oE, onu, oys
+
+
+class _PlbLossRot(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, sim, x, pp, pr, td, ts, wt, soft):
+        L = _lib.lib()
+        B = x.shape[0]
+        x, pp, pr = _c(x), _c(pp), _c(pr)
+        loss = torch.empty((B,), dtype=torch.float64, device=x.device)
+        parts = torch.empty((B, 3), dtype=torch.float64, device=x.device)
+        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        _lib.check(L.ud_plb_loss_fwd_rot(sim._h, C.c_int(B), _p(x), _p(pp), _p(pr), _p(td), _p(ts), _p(wt), C.c_int(int(soft)), _p(loss),
+                                         _p(parts), stream), "ud_plb_loss_fwd_rot")
+        ctx.sim, ctx.B, ctx.soft = sim, B, soft
+        ctx.save_for_backward(x, pp, pr, td, ts, wt)
+        ctx.mark_non_differentiable(parts)
+        return loss, parts
+
+    @staticmethod
+    def backward(ctx, gl, _gparts):
+        L = _lib.lib()
+        x, pp, pr, td, ts, wt = ctx.saved_tensors
+        gl = _c(gl)
+        gx, gpp, gpr = torch.empty_like(x), torch.empty_like(pp), torch.empty_like(pr)
+        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        _lib.check(L.ud_plb_loss_bwd_rot(ctx.sim._h, C.c_int(ctx.B), _p(x), _p(pp), _p(pr), _p(td), _p(ts), _p(wt), C.c_int(int(ctx.soft)),
+                                         _p(gl), _p(gx), _p(gpp), _p(gpr), stream), "ud_plb_loss_bwd_rot")
+        return None, gx, gpp, gpr, None, None, None, None
+
+
 class _PlbLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, sim, x, pp, td, ts, wt, soft):
@@ -186,6 +264,8 @@ class PlbSimulator:
         P = self.n_primitive
         pad = lambda seq, fill: (list(seq)[:P] + [fill] * 2)[:2]
         self.prim_kind = tuple(int(k) for k in pad(cfg.prim_kind, 0))[:P]
+        self.rot_state = bool(getattr(cfg, "rot_state", False))
+        self.action_dim = int(getattr(cfg, "action_dim", 3)) or 3
         rot = (C.c_double * 4 * 2)(*[(C.c_double * 4)(*q) for q in pad(cfg.prim_rot, (0.0, 0.0, 0.0, 0.0))])
         cc = _lib.ud_plb_conf(
             n_particles=self.n_particles, n_grid=self.n_grid, substeps=self.substeps, dt=self.dt,
@@ -194,7 +274,9 @@ class PlbSimulator:
             lower_bound=(C.c_double * 3)(*cfg.lower_bound), upper_bound=(C.c_double * 3)(*cfg.upper_bound),
             grid_ckpt_cells=int(self.grid_ckpt_cells), max_envs=int(batch_size), path=self.path, lanes=self.lanes, sort_every=self.sort_every,
             prim_kind=(C.c_int * 2)(*pad(cfg.prim_kind, 0)), capsule_h=(C.c_double * 2)(*pad(cfg.prim_h, 0.0)), prim_rot=rot,
-            prim_friction=(C.c_double * 2)(*pad(cfg.prim_friction, 0.0)), action_scale=(C.c_double * 3)(*cfg.action_scale))
+            prim_friction=(C.c_double * 2)(*pad(cfg.prim_friction, 0.0)), action_scale=(C.c_double * 3)(*cfg.action_scale),
+            rot_state=int(self.rot_state), action_dim=int(getattr(cfg, "action_dim", 3)),
+            action_scale_w=(C.c_double * 3)(*getattr(cfg, "action_scale_w", (1.0, 1.0, 1.0))))
         self._h = C.c_void_p()
         self.profile = None    # {"fwd": [], "bwd": []}: HIP-event pairs around every step call, on its stream (bench.py)
         self.ground_friction_grad = None   # [B], accumulated by backward() (optimize_ground_friction.grad); reset it by hand
@@ -248,13 +330,19 @@ class PlbSimulator:
                         softness=torch.full((B, self.n_primitive), float(cfg.softness), dtype=torch.float64, device=dev),   # set_softness()
                         E=torch.full((B,), float(cfg.E), dtype=torch.float64, device=dev),
                         nu=torch.full((B,), float(cfg.nu), dtype=torch.float64, device=dev),
-                        yield_stress=torch.full((B,), float(cfg.yield_stress), dtype=torch.float64, device=dev))
+                        yield_stress=torch.full((B,), float(cfg.yield_stress), dtype=torch.float64, device=dev),
+                        prim_rot=rep(f64([tuple(q) for q in list(cfg.prim_rot)[:self.n_primitive]])) if self.rot_state else None)
 
     def step(self, state: PlbState, action) -> PlbState:
         """TaichiEnv.step(action) in copy mode: one call = `substeps` substeps for every env.  Differentiable: when any of
         the state tensors / the action / E / nu / yield_stress requires grad, the forward keeps a checkpoint and backward()
         runs the adjoint kernels (substep_grad)."""
         B = state.x.shape[0]
+        if self.rot_state:      # action [B,action_dim]; the orientation is stepped with the position
+            action = torch.as_tensor(action, dtype=torch.float64, device=self.device).reshape(B, self.action_dim)
+            xo, vo, Co, Fo, po, ro = _PlbStepRot.apply(self, state.x, state.v, state.C, state.F, state.prim_pos, state.prim_rot, state.softness,
+                                                       action, state.E, state.nu, state.yield_stress)
+            return state._replace(x=xo, v=vo, C=Co, F=Fo, prim_pos=po, prim_rot=ro)
         action = torch.as_tensor(action, dtype=torch.float64, device=self.device).reshape(B, 3)
         xo, vo, Co, Fo, po = _PlbStep.apply(self, state.x, state.v, state.C, state.F, state.prim_pos, state.softness, action,
                                             state.E, state.nu, state.yield_stress)
@@ -267,6 +355,8 @@ class PlbSimulator:
         ts = torch.as_tensor(target_sdf, dtype=torch.float64, device=self.device).reshape(-1).contiguous()
         assert td.numel() == self.n_grid ** 3 == ts.numel()
         wt = torch.as_tensor(weights, dtype=torch.float64, device=self.device).reshape(3).contiguous()
+        if self.rot_state:
+            return _PlbLossRot.apply(self, state.x, state.prim_pos, state.prim_rot, td, ts, wt, bool(soft_contact))
         return _PlbLoss.apply(self, state.x, state.prim_pos, td, ts, wt, bool(soft_contact))
 
     @staticmethod
