@@ -4,8 +4,11 @@ tests/golden/cloth_adjoint_bits.npz (tests/test_cloth_adjoint_bits_gpu.py compar
 
 Run it against a build of the commit whose bits are the reference (UNIDOM_HIP_SO=/path/to/that/libunidom_hip.so), never to make a
 failing test pass.
-usage: python tools/record_cloth_adjoint_bits.py [--out FILE]"""
+usage: python tools/record_cloth_adjoint_bits.py [--cases MODULE] [--out FILE]
+  --cases: the module under tests/ that lists the cases (CASES, GOLDEN, case_id, run); default cloth_adjoint_bits_cases, or
+           cloth_bwd_unroll_cases for tests/golden/cloth_bwd_unroll_bits.npz (tests/test_cloth_bwd_unroll_bits_gpu.py)"""
 import argparse
+import importlib
 import os
 import sys
 
@@ -15,13 +18,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
 import cloth_adjoint_bar as cab                # noqa: E402
-import cloth_adjoint_bits_cases as cc          # noqa: E402
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden", cc.GOLDEN))
+    ap.add_argument("--cases", default="cloth_adjoint_bits_cases")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    cc = importlib.import_module(args.cases)
+    args.out = args.out or os.path.join(ROOT, "tests", "golden", cc.GOLDEN)
     from unidom_amd import _lib
     out = {}
     for case in cc.CASES:

@@ -24,6 +24,9 @@ __device__ __forceinline__ void st_lane(gfptr base, unsigned off, float val) {
   *(gfptr)((__attribute__((address_space(1))) char*)base + off) = val;
 }
 
+// x, from here on in a vector register (opaque to the compiler, which would otherwise keep a uniform value in a scalar one)
+__device__ __forceinline__ void vreg(float& x) { asm volatile("" : "+v"(x)); }
+
 template <typename G, typename T>
 __device__ __forceinline__ G uniform_ptr(T* p) {
   const unsigned long long u = (unsigned long long)p;
@@ -38,7 +41,9 @@ __device__ __forceinline__ G uniform_ptr(T* p) {
 // forward-only call carries neither block.  The substep loop is unrolled by two: with the parity of the LDS double buffer a
 // compile-time constant, buffer and plane offsets are immediates of the ds instructions and a neighbour's address is one
 // loop-invariant register.
-template <bool CKPT, bool GRASP>
+// ISV: the launch's constants passed cloth_isv_consts_ok, so isV comes from exact_math.h's select-free 1 / sqrt; the launch function runs
+// the `_anyc` kernels (the compiler's own 1.0f / sqrtf) where they do not.
+template <bool CKPT, bool GRASP, bool ISV>
 __device__ __forceinline__ void cloth_rollout_fwd_v2_body(const ClothFwdArgs& a) {
   extern __shared__ float ldsf[];  // Xs[2][3][UD_V2_MAXP], double-buffered by substep parity
   const ClothConst c = a.c;
@@ -56,8 +61,13 @@ __device__ __forceinline__ void cloth_rollout_fwd_v2_body(const ClothFwdArgs& a)
   float ps[8];
 #pragma unroll
   for (int d = 0; d < 8; ++d) ps[d] = a.prim[b * 8 + d];
-  const float k = a.k[b], mu = a.mu[b];
-  const f2 kL2 = {k / c.Ls, k / c.Ld};   // k / L0 with the rest lengths of cloth_simulator.py:61-63
+  float k = a.k[b], mu = a.mu[b];
+  float kLs = k / c.Ls, kLd = k / c.Ld;   // k / L0 with the rest lengths of cloth_simulator.py:61-63
+  // The stiffness and the friction coefficient multiply per-lane values in the link code: there a scalar operand costs a second
+  // issue slot at 2 waves/SIMD, so they live in vector registers for the whole launch.  Measured: -1.8 % of the kernel.
+  // The same for dt / damp / max_v / g or for the bounds of the |r|^2 clip made it slower (profiles/r09_ablation.txt).
+  vreg(k); vreg(mu); vreg(kLs); vreg(kLd);
+  const f2 kL2 = {kLs, kLd};
   GraspThr th0, th1;
   th0.init(ps[3]); th1.init(ps[7]);
   float thr0 = th0.first, thr1 = th1.first;   // loop-carried: `rest` from the second substep on, instead of a select per substep
@@ -90,7 +100,8 @@ __device__ __forceinline__ void cloth_rollout_fwd_v2_body(const ClothFwdArgs& a)
     bool m0, m1;
     grip_own(x, ps, act, thr0, thr1, m0, m1, x2);
     thr0 = th0.rest; thr1 = th1.rest;
-    const float isV = 1.0f / sqrtf(v[0] * v[0] + v[2] * v[2] + c.eps);
+    const float sV = v[0] * v[0] + v[2] * v[2] + c.eps;
+    const float isV = ISV ? rcp_sqrt_rn_rsq(sV) : 1.0f / sqrtf(sV);
 #pragma unroll
     for (int g = 0; g < 2; ++g)
 #pragma unroll
@@ -156,15 +167,23 @@ __device__ __forceinline__ void cloth_rollout_fwd_v2_body(const ClothFwdArgs& a)
 
 // One kernel per variant, each under a plain name (profiles and counter passes are keyed by kernel name): the training forward
 // (checkpoints, no grasp sets) keeps the name it always had.
-__global__ void __launch_bounds__(512) cloth_rollout_fwd_v2_kernel(ClothFwdArgs a) { cloth_rollout_fwd_v2_body<true, false>(a); }
-__global__ void __launch_bounds__(512) cloth_rollout_fwd_v2_eval_kernel(ClothFwdArgs a) { cloth_rollout_fwd_v2_body<false, false>(a); }
-__global__ void __launch_bounds__(512) cloth_rollout_fwd_v2_grasp_kernel(ClothFwdArgs a) { cloth_rollout_fwd_v2_body<false, true>(a); }
-__global__ void __launch_bounds__(512) cloth_rollout_fwd_v2_ckpt_grasp_kernel(ClothFwdArgs a) { cloth_rollout_fwd_v2_body<true, true>(a); }
+__global__ void __launch_bounds__(512) cloth_rollout_fwd_v2_kernel(ClothFwdArgs a) { cloth_rollout_fwd_v2_body<true, false, true>(a); }
+__global__ void __launch_bounds__(512) cloth_rollout_fwd_v2_eval_kernel(ClothFwdArgs a) { cloth_rollout_fwd_v2_body<false, false, true>(a); }
+__global__ void __launch_bounds__(512) cloth_rollout_fwd_v2_grasp_kernel(ClothFwdArgs a) { cloth_rollout_fwd_v2_body<false, true, true>(a); }
+__global__ void __launch_bounds__(512) cloth_rollout_fwd_v2_ckpt_grasp_kernel(ClothFwdArgs a) { cloth_rollout_fwd_v2_body<true, true, true>(a); }
+// the same four for constants outside cloth_isv_consts_ok
+__global__ void __launch_bounds__(512) cloth_rollout_fwd_v2_anyc_kernel(ClothFwdArgs a) { cloth_rollout_fwd_v2_body<true, false, false>(a); }
+__global__ void __launch_bounds__(512) cloth_rollout_fwd_v2_eval_anyc_kernel(ClothFwdArgs a) { cloth_rollout_fwd_v2_body<false, false, false>(a); }
+__global__ void __launch_bounds__(512) cloth_rollout_fwd_v2_grasp_anyc_kernel(ClothFwdArgs a) { cloth_rollout_fwd_v2_body<false, true, false>(a); }
+__global__ void __launch_bounds__(512) cloth_rollout_fwd_v2_ckpt_grasp_anyc_kernel(ClothFwdArgs a) { cloth_rollout_fwd_v2_body<true, true, false>(a); }
 
 void cloth_launch_fwd_v2(const ClothFwdArgs& a, hipStream_t stream) {
   const size_t shmem = (size_t)2 * 3 * UD_V2_MAXP * sizeof(float);
   auto* kern = a.ckpt ? (a.grasp ? cloth_rollout_fwd_v2_ckpt_grasp_kernel : cloth_rollout_fwd_v2_kernel)
                       : (a.grasp ? cloth_rollout_fwd_v2_grasp_kernel : cloth_rollout_fwd_v2_eval_kernel);
+  if (!cloth_isv_consts_ok(a.c))
+    kern = a.ckpt ? (a.grasp ? cloth_rollout_fwd_v2_ckpt_grasp_anyc_kernel : cloth_rollout_fwd_v2_anyc_kernel)
+                  : (a.grasp ? cloth_rollout_fwd_v2_grasp_anyc_kernel : cloth_rollout_fwd_v2_eval_anyc_kernel);
   hipLaunchKernelGGL(kern, dim3(a.B), dim3(a.c.Pp), shmem, stream, a);
 }
 

@@ -31,6 +31,14 @@ __device__ __forceinline__ void grip_own(const float* x, const float* ps, const 
   for (int a = 0; a < 3; ++a) x2[a] = m1 ? x1[a] + act[4 + a] * (1.f - act[7]) : x1[a];
 }
 
+// isV = 1.0f / sqrtf(xV^2 + yV^2 + small_num) may be taken from rcp_sqrt_rn_rsq when the launch's constants keep its argument inside that
+// function's range: small_num >= 2^-96 bounds it from below (squares are >= 0; a NaN velocity stays NaN), and a max_v whose clipped
+// velocities cannot overflow the sum from above (an unclipped input velocity still can, on the first substep: the function's +inf case).
+__host__ __device__ inline bool cloth_isv_consts_ok(const ClothConst& c) {
+  return c.eps >= 0x1p-96f && c.eps <= FLT_MAX && c.max_v == c.max_v &&
+         2.0 * (double)c.max_v * (double)c.max_v + (double)c.eps <= (double)FLT_MAX;
+}
+
 // spring + gravity + ground friction + damping in the re-associated IEEE order "v2"
 // (oracle/csrc/cloth_oracle.hpp::cloth_substep_fwd_v2): only +,-,*,/,sqrt, no FMA contraction in this file.
 // Links are processed as PAIRS (straight link p, diagonal link p+4) in float2 = v_pk_{add,mul,fma}_f32, which are
@@ -58,7 +66,7 @@ __device__ __forceinline__ void force_v2(const ClothConst& c, const int* nbs, co
     // which k/L0 - k/len rounds to the same float) and len in [1e-6, 2^64]: the exact_math.h ranges
     cl[p] = f2{fminf(fmaxf(s2.x, 1e-12f), FLT_MAX), fminf(fmaxf(s2.y, 1e-12f), FLT_MAX)};
   }
-  rcp_sqrt_rn_inrange2x4(cl, inv);   // 1 / sqrt, both correctly rounded
+  rcp_sqrt_rn_rsq2x4(cl, inv);   // 1 / sqrt, both correctly rounded: the bits of rcp_sqrt_rn_inrange2x4 without its selects
   f2 F0 = {0.f, 0.f}, F1 = {0.f, 0.f}, F2 = {0.f, 0.f};
 #pragma unroll
   for (int p = 0; p < 4; ++p) {

@@ -137,4 +137,68 @@ __device__ __forceinline__ void rcp_sqrt_rn_inrange2x4(const f2 (&x)[4], f2 (&ou
   for (int p = 0; p < 4; ++p) out[p] = __builtin_elementwise_fma(e[p], r[p], q[p]);
 }
 
+// The same value, RN(1 / RN(sqrt(x))), without a compare, a select or an integer add: both roundings are unique, so any sequence that
+// reaches them returns rcp_sqrt_rn_inrange2x4's bits.  The root is the compiler's OTHER IEEE expansion of sqrtf (AMDGPU lowerFSQRTF32, the
+// v_rsq_f32 seed): y = rsq(x), g = x y, h = y / 2, one coupled Newton step on (g, h), then the residual x - g^2 corrected through h.  The
+// reciprocal is rcp_rn_inrange's chain from v_rcp_f32(s).  (Seeding that chain with 2 h, which is 1 / s to about an ulp, would save the
+// second transcendental, but misses the correctly rounded reciprocal for 168 of the 1.4e9 arguments in [1e-12f, FLT_MAX], the first of
+// them 0x2c7ffffe, with or without the chain's first refinement step: measured on an MI355X, not shipped.)
+// For 2^-96 <= x <= FLT_MAX; NaN gives NaN; +inf gives NaN, NOT 0 (rsq(inf) * inf) -- see rcp_sqrt_rn_rsq for the scalar form that
+// repairs it.  Bit-equal to rcp_sqrt_rn_inrange2x4 for every float in [1e-12f, FLT_MAX] and to 1.0f / sqrtf(x) below it
+// (tests/test_exact_math_rsq_gpu.py walks all of them on the GPU).
+__device__ __forceinline__ void rcp_sqrt_rn_rsq2x4(const f2 (&x)[4], f2 (&out)[4]) {
+  const f2 one = {1.0f, 1.0f}, half = {0.5f, 0.5f};
+  f2 g[4], h[4], e[4], d[4], s[4], r[4], q[4];
+#pragma unroll
+  for (int p = 0; p < 4; ++p) h[p] = f2{__builtin_amdgcn_rsqf(x[p].x), __builtin_amdgcn_rsqf(x[p].y)};
+#pragma unroll
+  for (int p = 0; p < 4; ++p) g[p] = x[p] * h[p];
+#pragma unroll
+  for (int p = 0; p < 4; ++p) h[p] = h[p] * half;
+#pragma unroll
+  for (int p = 0; p < 4; ++p) e[p] = __builtin_elementwise_fma(-h[p], g[p], half);
+#pragma unroll
+  for (int p = 0; p < 4; ++p) g[p] = __builtin_elementwise_fma(g[p], e[p], g[p]);
+#pragma unroll
+  for (int p = 0; p < 4; ++p) h[p] = __builtin_elementwise_fma(h[p], e[p], h[p]);
+#pragma unroll
+  for (int p = 0; p < 4; ++p) d[p] = __builtin_elementwise_fma(-g[p], g[p], x[p]);
+#pragma unroll
+  for (int p = 0; p < 4; ++p) s[p] = __builtin_elementwise_fma(d[p], h[p], g[p]);      // RN(sqrt(x))
+#pragma unroll
+  for (int p = 0; p < 4; ++p) r[p] = f2{__builtin_amdgcn_rcpf(s[p].x), __builtin_amdgcn_rcpf(s[p].y)};
+#pragma unroll
+  for (int p = 0; p < 4; ++p) e[p] = __builtin_elementwise_fma(-s[p], r[p], one);
+#pragma unroll
+  for (int p = 0; p < 4; ++p) r[p] = __builtin_elementwise_fma(e[p], r[p], r[p]);
+#pragma unroll
+  for (int p = 0; p < 4; ++p) e[p] = __builtin_elementwise_fma(-s[p], r[p], one);
+#pragma unroll
+  for (int p = 0; p < 4; ++p) q[p] = __builtin_elementwise_fma(e[p], r[p], r[p]);
+#pragma unroll
+  for (int p = 0; p < 4; ++p) e[p] = __builtin_elementwise_fma(-s[p], q[p], one);
+#pragma unroll
+  for (int p = 0; p < 4; ++p) out[p] = __builtin_elementwise_fma(e[p], r[p], q[p]);
+}
+
+// The scalar form: 1.0f / sqrtf(x) for 2^-96 <= x <= +inf and NaN (the one select is +inf's, where the sequence itself gives NaN).
+__device__ __forceinline__ float rcp_sqrt_rn_rsq(float x) {
+  float h = __builtin_amdgcn_rsqf(x);
+  float g = x * h;
+  h = h * 0.5f;
+  float e = __builtin_fmaf(-h, g, 0.5f);
+  g = __builtin_fmaf(g, e, g);
+  h = __builtin_fmaf(h, e, h);
+  const float d = __builtin_fmaf(-g, g, x);
+  const float s = __builtin_fmaf(d, h, g);
+  float r = __builtin_amdgcn_rcpf(s);
+  e = __builtin_fmaf(-s, r, 1.0f);
+  r = __builtin_fmaf(e, r, r);
+  e = __builtin_fmaf(-s, r, 1.0f);
+  const float q = __builtin_fmaf(e, r, r);
+  e = __builtin_fmaf(-s, q, 1.0f);
+  const float o = __builtin_fmaf(e, r, q);
+  return x == __builtin_inff() ? 0.0f : o;
+}
+
 }  // namespace ud
