@@ -17,7 +17,7 @@
 namespace ud {
 
 constexpr int GLUE_T = 256;       // threads per workgroup
-constexpr int GLUE_MAXPTS = 4096; // points per cloud staged in LDS (12 floats/point budget: 2 clouds = 96 KB)
+constexpr int GLUE_MAXPTS = 4096; // points per cloud staged in LDS: 48 KB in the chamfer forward, 52 KB in its backward (3 P + 1024 floats)
 
 __device__ __forceinline__ float mean_sq3(float ax, float ay, float az, float bx, float by, float bz) {
   const float dx = ax - bx, dy = ay - by, dz = az - bz;
@@ -235,11 +235,15 @@ __global__ void __launch_bounds__(GLUE_T) pnp_bwd_kernel(int B, int P, const flo
       for (int d = 0; d < 3; ++d) move[d] += g_macro[((size_t)t * B + b) * 8 + d];
     for (int d = 0; d < 3; ++d) { down[d] *= R3; move[d] *= R20; }
     // contact = |pick - x_p*|: d/dpick = (pick - x_p*) / contact, d/dx_p* = -(...)
+    // A null g_contact means contact_distance is not in the graph (aux_reward off): no contact term at all, as in the reference --
+    // 0 * ((pick - x_p*) / contact) would be NaN with the pick on a particle or a non-finite nearest particle.
     const int p = contact_idx[b];
-    const float gc = g_contact ? g_contact[b] : 0.f;
     const float* a = actions + b * 6;
-    float cg[3];
-    for (int d = 0; d < 3; ++d) cg[d] = gc * ((a[d] - x[((size_t)b * P + p) * 3 + d]) / contact[b]);
+    float cg[3] = {0.f, 0.f, 0.f};
+    if (g_contact) {
+      const float gc = g_contact[b];
+      for (int d = 0; d < 3; ++d) cg[d] = gc * ((a[d] - x[((size_t)b * P + p) * 3 + d]) / contact[b]);
+    }
     g_actions[b * 6 + 0] = down[0] - move[0] + cg[0];
     g_actions[b * 6 + 1] = cg[1];                       // pick.y is zeroed before the expansion (:145)
     g_actions[b * 6 + 2] = down[2] - move[2] + cg[2];
@@ -247,7 +251,8 @@ __global__ void __launch_bounds__(GLUE_T) pnp_bwd_kernel(int B, int P, const flo
     g_actions[b * 6 + 4] = 0.f;                          // place.y zeroed (:146)
     g_actions[b * 6 + 5] = move[2];
     g_prim0[b * 4 + 0] = -down[0]; g_prim0[b * 4 + 1] = -down[1]; g_prim0[b * 4 + 2] = -down[2]; g_prim0[b * 4 + 3] = 0.f;
-    for (int d = 0; d < 3; ++d) gxb[p * 3 + d] = -cg[d];
+    if (g_contact)
+      for (int d = 0; d < 3; ++d) gxb[p * 3 + d] = -cg[d];
   }
 }
 

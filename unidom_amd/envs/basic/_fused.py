@@ -61,6 +61,9 @@ class PnpContactFn(torch.autograd.Function):
         _lib.check(_lib.lib().ud_cloth_pnp_fwd(C.c_int(B), C.c_int(P), _lib.ptr(a), _lib.ptr(p0), _lib.ptr(xc), _lib.ptr(macro),
                                                _lib.ptr(contact), _lib.ptr(idx), _stream(xc.device)), "ud_cloth_pnp_fwd")
         ctx.save_for_backward(a, xc, contact, idx)
+        # an unused output's cotangent arrives as None, not as zeros: the kernel then adds no contact term (aux_reward off), where
+        # 0 * d contact would be NaN with the pick on a particle
+        ctx.set_materialize_grads(False)
         return macro, contact
 
     @staticmethod
