@@ -76,6 +76,31 @@ struct GraspThr {
   __device__ __forceinline__ float at(bool first_substep) const { return first_substep ? first : rest; }
 };
 
+// Issue priority of the one-workgroup rollout kernels at two waves per SIMD (bodies of 257-512 padded particles: wave w shares its
+// SIMD with wave w + 4).  The SIMD arbitrates VALU issue by priority, then age: at equal priority the first-dispatched wave runs nearly
+// unimpeded, its partner gets the leftover slots, arrives late at every barrier, and while it finishes alone the SIMD issues at one
+// wave's rate (measured: waves 0-3 waited a third of every substep at the barriers, waves 4-7 not at all;
+// profiles/r10_wave_stamps.txt).  So the losing wave enters every barrier interval at priority 1 (`up`, in front of the barrier that
+// opens it) and drops to 0 part-way through (`drop`), where age hands the SIMD to its partner and both reach the next barrier together.
+// s_setprio is a scalar instruction that ignores EXEC: `lose` is wave-uniform (readfirstlane) and the kernels branch on it ONCE,
+// into a copy of their loop with the priority changes or into one without any.  A wave with no partner on its SIMD (every wave of a body
+// of at most 256 padded particles, waves 1-3 of a 5-wave body) and a body of more than 8 waves run the copy without.
+struct WavePrio {
+  bool lose;
+  __device__ __forceinline__ void init(int Pp) {
+    const int w = __builtin_amdgcn_readfirstlane((int)threadIdx.x) >> 6;
+    lose = w >= 4 && Pp <= 512;   // waves 4-7 were the later-dispatched half in every workgroup sampled
+  }
+  static __device__ __forceinline__ void up() { __builtin_amdgcn_s_setprio(1); }
+  // pinned against the instruction scheduler; arithmetic that the optimiser moves before scheduling can still cross it, so the place is
+  // read off the ISA (tools/asm_loop_stats.py --dump) at every change of the surrounding code
+  static __device__ __forceinline__ void drop() {
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+};
+
 void cloth_launch_fwd_v2(const ClothFwdArgs& a, hipStream_t stream);
 bool cloth_ref_consts_ok(const ClothConst& c);                                 // cloth_ref.hip: the mode-3 fast path's per-launch constant checks
 bool cloth_ref_fast_ok(const ClothConst& c);                                   // ... and Pp <= 512: cloth_ref.hip's kernel may run

@@ -9,6 +9,7 @@
 // The choices themselves are those the compiler made for the build this file was split from (contraction on, SLP vectoriser on),
 // read off its ISA (tools/isa_dataflow.py) and pinned by tests/test_cloth_adjoint_bits_gpu.py: they look arbitrary in places
 // (sm[3] and sm[5] unfused, sm[4] half fused, the nm sum of the norm chain fused differently from n2v) because they were.
+#include <type_traits>
 #include "cloth_fast_adj.h"
 
 #pragma clang fp contract(off)
@@ -124,6 +125,13 @@ __device__ __forceinline__ void cloth_rollout_bwd_fast(const ClothBwdArgs& a, fl
   __syncthreads();
   unsigned step = 0;
   const float* rp = ck + ((size_t)T * S - 1) * rec;   // record held in nx/nv/nps
+  // Two waves per SIMD (WavePrio, cloth_common.h): the wave that loses the SIMD's arbitration enters both barrier intervals of the substep
+  // at priority 1 and drops to 0 after force_pairs_x in the one, at the end of the spring adjoint in the other.  Either hand-over alone only moves the older
+  // wave's wait to the other barrier (no gain); both together: -7 % of the kernel (profiles/r10_ablation.txt).
+  WavePrio wp;
+  wp.init(Pp);
+  auto sweep = [&](auto lose) {
+  constexpr bool LOSE = decltype(lose)::value;
   for (int t = T - 1; t >= 0; --t) {
     if (live) {
       const size_t o = (((size_t)t * B + b) * P + i) * 3;
@@ -186,6 +194,7 @@ __device__ __forceinline__ void cloth_rollout_bwd_fast(const ClothBwdArgs& a, fl
           rd[wv * UD_RSTR + 8] = 0.f;
         }
       }
+      if (LOSE) wp.up();
       __syncthreads();   // barrier 1: X4 and the wave partials are visible
       float sx = 1.f, sv = 1.f, sA = 1.f, sB = 1.f, s3x = 1.f, s3v = 1.f;   // cumulative scale factors
       if (NORM) {
@@ -220,6 +229,7 @@ __device__ __forceinline__ void cloth_rollout_bwd_fast(const ClothBwdArgs& a, fl
       float v3[3], v4[3];
       PairInter in;
       force_pairs_x<UD_CLOTH_MAXP>(c, nbs, Xs, k, iL2, mu, x, v, v3, &in);
+      if (LOSE) wp.drop();
 #pragma unroll
       for (int d = 0; d < 3; ++d) v4[d] = m0 ? act[3] * v3[d] : v3[d];
       // ---- reverse: clip (:326-329) and the two grippers (:313-314) with their normalisations folded in ----
@@ -273,6 +283,7 @@ __device__ __forceinline__ void cloth_rollout_bwd_fast(const ClothBwdArgs& a, fl
         gv[0] = g2x + gxV; gv[1] = g2y; gv[2] = g2z + gyV;   // v1 = v - (0, g dt, 0)
       }
       Gs[i] = gF[0]; Gs[UD_CLOTH_MAXP + i] = gF[1]; Gs[2 * UD_CLOTH_MAXP + i] = gF[2];
+      if (LOSE) wp.up();
       __syncthreads();   // barrier 2: Gs visible
 #pragma unroll
       for (int d = 0; d < 8; ++d) ps[d] = nps[d];   // next substep's primitives
@@ -301,6 +312,7 @@ __device__ __forceinline__ void cloth_rollout_bwd_fast(const ClothBwdArgs& a, fl
       gx[0] = ax0; gx[1] = ax1; gx[2] = ax2;
 #pragma unroll
       for (int d = 0; d < 3; ++d) vnext[d] = v[d];   // this substep's input v is the previous substep's clip(v5)
+      if (LOSE) wp.drop();
     }
     // macro-step boundary: robot_step's action transform (:168-169)
     {
@@ -319,6 +331,9 @@ __device__ __forceinline__ void cloth_rollout_bwd_fast(const ClothBwdArgs& a, fl
       }
     }
   }
+  };
+  // two copies of the sweep, chosen per wave: every wave passes the same barriers in either
+  if (wp.lose) sweep(std::true_type()); else sweep(std::false_type());
   if (live) {
     const size_t o = ((size_t)b * P + i) * 3;
 #pragma unroll

@@ -4,7 +4,8 @@
 // over a whole 2000-substep step_diff, including the discrete grasp sets.  Against the reference's
 // literal order (cloth.hip, mode 1) it differs by f32 round-off per substep -- see DESIGN.md "Numerical sensitivity".
 // Same mapping as the other cloth kernels: one workgroup per env, one particle per lane, float4 positions
-// double-buffered in LDS, one barrier per substep, per-substep checkpoints to HBM.
+// double-buffered in LDS, one barrier per substep, per-substep checkpoints to HBM.  Bodies of 257-512 padded particles run two waves per
+// SIMD: there the later-dispatched wave of each SIMD changes its issue priority inside every substep (WavePrio, cloth_common.h).
 #include <type_traits>
 #include "cloth_v2_force.h"
 
@@ -80,9 +81,12 @@ __device__ __forceinline__ void cloth_rollout_fwd_v2_body(const ClothFwdArgs& a)
 #pragma unroll
   for (int d = 0; d < 3; ++d) { ox[d] = 4u * (unsigned)(d * Pp + i); ov[d] = 4u * (unsigned)((3 + d) * Pp + i); }
   float act[8];
-  // one substep on LDS buffer PAR
-  auto substep = [&](auto par) {
+  WavePrio wp;
+  wp.init(Pp);
+  // one substep on LDS buffer PAR; LOSE: this wave loses the SIMD's arbitration to its partner (wave-uniform, decided once below)
+  auto substep = [&](auto par, auto lose) {
     constexpr int PAR = decltype(par)::value;
+    constexpr bool LOSE = decltype(lose)::value;
     float* Xs = ldsf + PAR * (3 * UD_V2_MAXP);
     Xs[i] = x[0]; Xs[UD_V2_MAXP + i] = x[1]; Xs[2 * UD_V2_MAXP + i] = x[2];
     if (CKPT) {
@@ -106,6 +110,7 @@ __device__ __forceinline__ void cloth_rollout_fwd_v2_body(const ClothFwdArgs& a)
     for (int g = 0; g < 2; ++g)
 #pragma unroll
       for (int d = 0; d < 4; ++d) ps[g * 4 + d] = clipf(ps[g * 4 + d] + (d < 3 ? act[g * 4 + d] : 0.f), 0.f, 1.f);  // :322-323
+    if (LOSE) wp.up();
     __syncthreads();
     force_v2<UD_V2_MAXP>(c, nbs, Xs, k, kL2, mu, x, v, isV, vv);
 #pragma unroll
@@ -123,28 +128,35 @@ __device__ __forceinline__ void cloth_rollout_fwd_v2_body(const ClothFwdArgs& a)
       x[d] = clipf(x2[d], 0.f, 1.f) + c.dt * vc;
       v[d] = vc;
     }
+    // the hand-over: the force and the update are done, the partner wave takes the SIMD while this one writes the next substep's
+    // positions and record and runs its own-particle block (the best of six places tried, profiles/r10_ablation.txt)
+    if (LOSE) wp.drop();
   };
-  for (int t = 0; t < T; ++t) {
-    macro_action_f(a.actions + ((size_t)t * B + b) * 8, act);
-    int s = 0;
-    for (; s + 1 < S; s += 2) {
-      substep(std::integral_constant<int, 0>());
-      substep(std::integral_constant<int, 1>());
-    }
-    if (s < S) {   // odd S: the next macro step starts on buffer 0 again, whose readers of this substep must be done first
-      substep(std::integral_constant<int, 0>());
-      __syncthreads();
-    }
-    if (live) {
-      const size_t o = (((size_t)t * B + b) * P + i) * 3;
-      if (a.x_list) { a.x_list[o] = x[0]; a.x_list[o + 1] = x[1]; a.x_list[o + 2] = x[2]; }
-      if (a.v_list) { a.v_list[o] = v[0]; a.v_list[o + 1] = v[1]; a.v_list[o + 2] = v[2]; }
-    }
-    if (a.prim_list && i == 0) {
+  auto rollout = [&](auto lose) {
+    for (int t = 0; t < T; ++t) {
+      macro_action_f(a.actions + ((size_t)t * B + b) * 8, act);
+      int s = 0;
+      for (; s + 1 < S; s += 2) {
+        substep(std::integral_constant<int, 0>(), lose);
+        substep(std::integral_constant<int, 1>(), lose);
+      }
+      if (s < S) {   // odd S: the next macro step starts on buffer 0 again, whose readers of this substep must be done first
+        substep(std::integral_constant<int, 0>(), lose);
+        __syncthreads();
+      }
+      if (live) {
+        const size_t o = (((size_t)t * B + b) * P + i) * 3;
+        if (a.x_list) { a.x_list[o] = x[0]; a.x_list[o + 1] = x[1]; a.x_list[o + 2] = x[2]; }
+        if (a.v_list) { a.v_list[o] = v[0]; a.v_list[o + 1] = v[1]; a.v_list[o + 2] = v[2]; }
+      }
+      if (a.prim_list && i == 0) {
 #pragma unroll
-      for (int d = 0; d < 8; ++d) a.prim_list[((size_t)t * B + b) * 8 + d] = ps[d];
+        for (int d = 0; d < 8; ++d) a.prim_list[((size_t)t * B + b) * 8 + d] = ps[d];
+      }
     }
-  }
+  };
+  // two copies of the loop, chosen per wave: every wave passes the same barriers in either
+  if (wp.lose) rollout(std::true_type()); else rollout(std::false_type());
   if (live) {
     const size_t o = ((size_t)b * P + i) * 3;
 #pragma unroll
