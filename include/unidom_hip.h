@@ -451,6 +451,39 @@ int ud_plb_loss_bwd_rot(ud_plb* h, int B, const double* x, const double* prim_po
                         const double* target_sdf, const double* weights, int soft_contact, const double* g_loss, double* g_x,
                         double* g_prim_pos, double* g_prim_rot, void* stream);
 
+/* Grid mass of a particle state, the field a goal is made of (TaichiEnv.get_grid_mass; create_goal1.py saves it as the target
+ * density): grid_mass [B, n_grid^3] = the loss's p2g of the particle masses, written into the caller's array (zeroed here, summed with
+ * atomics).  Any handle kind and path; B is not bound by max_envs: the call reads the handle's constants only and touches none of its
+ * arenas, so it may run next to a loss call of the same handle on another stream. */
+int ud_plb_grid_mass(ud_plb* h, int B, const double* x, double* grid_mass, void* stream);
+
+/* Target SDF of T target densities (Loss.update_target / update_target_sdf, engine/losses/loss.py:77-106), handle-free: launches only,
+ * no allocation, no synchronisation, capturable in a HIP graph.  G = n_grid^3, cell (i,j,k) at (i n + j) n + k; density, sdf [T,G].
+ * State per cell: S (distance, 1000 = none yet) and P (the occupied cell nearest so far); S_c = 1000 everywhere at the start.  One
+ * sweep, for every cell I from the copies (S_c, P_c) of the previous sweep:
+ *   density[I] > threshold: S = 0, P = I;
+ *   otherwise S = 1000, then for every offset o in {-3..2}^3 without 0, lexicographic with ox slowest, v = I + o inside the grid and
+ *   S_c[v] < 1000:  d = sqrt(dx^2 + dy^2 + dz^2 + 1e-8) of x_I - x_{P_c[v]} with x_J = J * (1 / n_grid), summed left to right;
+ *   d < S (strict): S = d, P = P_c[v].
+ * The window is asymmetric (3 cells down, 2 up), the first minimal candidate in offset order wins, and a cell is recomputed in every
+ * sweep.  sweeps = 0 runs the reference's 2 n_grid sweeps, sweeps = k exactly k.  One launch per sweep, all enqueued; a launch whose
+ * predecessor changed no cell of its target returns at entry (a fixed point of a deterministic map stays one), so the outputs are those
+ * of all the sweeps: sdf = S; nearest [T,G] (may be NULL) = linear index of P, -1 where S = 1000; sweeps_run [T] (device, may be NULL) =
+ * the number of sweeps that did work for that target = min(sweeps, 1-based number of the first sweep that changed nothing).
+ * work: ud_plb_target_work_bytes(n_grid, T) bytes (two int32 states per cell + one word per target; 0 for sizes the call rejects).
+ * n_grid < 1, T < 1, sweeps < 0, null density / sdf / work: UD_ERR_INVALID; n_grid > 1024 (P is packed into 3 x 10 bits) or
+ * T > 65535: UD_ERR_UNSUPPORTED.  Results are bit-identical from run to run. */
+size_t ud_plb_target_work_bytes(int n_grid, int T);
+int ud_plb_target_sdf(int n_grid, int T, const double* density, double threshold, int sweeps, double* sdf, int* nearest,
+                      int* sweeps_run, void* work, void* stream);
+
+/* Soft IoU of densities (iou_kernel, loss.py:239-254): a [T,G]; b [T,G] (b_batched != 0) or [G] shared by all t; iou [T].
+ *   ma = max(0, max a), mb = max(0, max b), I = sum(a b) / ma / mb, U = sum(a) / ma + sum(b) / mb, iou = I / (U - I).
+ * Every sum runs in a fixed order (two stages of binary trees): the same input gives the same bits.  ma = 0 or mb = 0 is not
+ * special-cased: the result is what IEEE gives (0 / 0 = NaN).  work: ud_plb_density_iou_work_bytes(T) bytes.  Launches only. */
+size_t ud_plb_density_iou_work_bytes(int T);
+int ud_plb_density_iou(long G, int T, const double* a, const double* b, int b_batched, double* iou, void* work, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Cloth-env arithmetic either side of the rollout (the reference jit-fuses it into step_diff; here one forward and
  * one backward kernel per piece, one workgroup per env, instead of ~180 elementwise launches per step_diff).

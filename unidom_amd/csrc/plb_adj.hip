@@ -883,3 +883,16 @@ int ud_plb_loss_bwd_rot(ud_plb* h, int B, const double* x, const double* prim_po
 }
 
 }  // extern "C"
+
+// the loss's grid mass handed out (Loss.grid_mass after compute_grid_m_kernel; TaichiEnv.get_grid_mass): the same kernel into the caller's
+// array.  It reads only the handle's constants, so it runs next to a loss call on another stream
+extern "C" int ud_plb_grid_mass(ud_plb* h, int B, const double* x, double* grid_mass, void* stream) {
+  if (!h || !x || !grid_mass) { ud::set_error("ud_plb_grid_mass: null argument"); return UD_ERR_INVALID; }
+  if (B < 1 || B > 65535) { ud::set_error("ud_plb_grid_mass: B=%d", B); return UD_ERR_INVALID; }
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(grid_mass, 0, (size_t)B * h->G * 8, st) != hipSuccess) { ud::set_error("ud_plb_grid_mass: memset failed"); return UD_ERR_HIP; }
+  hipLaunchKernelGGL(ud::plb_loss_mass, dim3((h->c.N + 255) / 256, B), dim3(256), 0, st, h->c, h->G, x, grid_mass);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { ud::set_error("ud_plb_grid_mass: %s", hipGetErrorString(e)); return UD_ERR_HIP; }
+  return UD_OK;
+}

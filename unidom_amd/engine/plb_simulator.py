@@ -359,6 +359,16 @@ class PlbSimulator:
             return _PlbLossRot.apply(self, state.x, state.prim_pos, state.prim_rot, td, ts, wt, bool(soft_contact))
         return _PlbLoss.apply(self, state.x, state.prim_pos, td, ts, wt, bool(soft_contact))
 
+    def get_grid_mass(self, state: PlbState):
+        """TaichiEnv.get_grid_mass: the loss's grid mass of the state, [B, n_grid, n_grid, n_grid] (ud_plb_grid_mass).  A goal's target
+        density is this field of the goal state.  No gradient."""
+        x = _c(state.x)
+        B, n = x.shape[0], self.n_grid
+        gm = torch.empty((B, n, n, n), dtype=torch.float64, device=x.device)
+        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        _lib.check(_lib.lib().ud_plb_grid_mass(self._h, C.c_int(B), _p(x), _p(gm), stream), "ud_plb_grid_mass")
+        return gm
+
     @staticmethod
     def set_softness1(state: PlbState, softness) -> PlbState:   # primitives.py: Primitives.set_softness1
         so = state.softness.clone()
