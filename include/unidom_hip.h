@@ -484,6 +484,42 @@ int ud_plb_target_sdf(int n_grid, int T, const double* density, double threshold
 size_t ud_plb_density_iou_work_bytes(int T);
 int ud_plb_density_iou(long G, int T, const double* a, const double* b, int b_batched, double* iou, void* work, void* stream);
 
+/* System identification (PlasticineLab sim2sim / real2sim: optimizer/solver.py, engine/losses/loss.py new_target_density[f]):
+ * the density loss of a SEQUENCE of particle clouds, each against a target of its own, with its adjoint (csrc/plb_sysid.hip).
+ * An item is one cloud; the M items are any flattening of frames x envs.  Like ud_plb_grid_mass the calls read the handle's constants
+ * only and touch none of its arenas: M is not bound by max_envs, any handle kind and path.  Launches only: no allocation, no
+ * synchronisation, capturable in a HIP graph; no workgroup waits for another one.  G = n_grid^3.
+ *   x [M,N,3]; targets [T,G]; target_index [M] (device int32; NULL = target 0 for every item); loss [M]:
+ *   loss[m] = sum_I |gm_I(x_m) - targets[target_index[m], I]|, gm = the mass p2g of ud_plb_loss_fwd / ud_plb_grid_mass (same weights,
+ *   same clamping of the cell indices into the grid).
+ * The forward works in chunks of work_bytes / (8 G) items: a chunk's masses are scattered with f64 atomics into `work` (zeroed by a
+ * kernel), then one sweep per chunk reads gm and the target, reduces |df| per item, records sign(df) and leaves the scratch zero for
+ * the next chunk.  The result does not depend on the chunking beyond the order of the atomic sums.  work_bytes below one item (8 G):
+ * UD_ERR_INVALID.  ud_plb_density_seq_work_bytes(h, M) = 8 G min(M, C) with C = the items that fit into 256 MiB (at least one, at
+ * most 65535): never more than max(256 MiB, 8 G).
+ * sign (may be NULL = no backward): ud_plb_density_seq_sign_bytes(h, M) bytes (2 bits per cell and item, 16-byte aligned), opaque;
+ * three-valued, 0 where df == 0, as ud_plb_loss_bwd decides it (an empty cell of an empty target sends nothing).
+ * A target_index[m] outside [0, T) reads nothing out of bounds: loss[m] = NaN, that item's sign field is all zero, so its g_x is 0.
+ * ud_plb_density_seq_bwd: g_x[m,p] = inv_dx g_loss[m] p_mass sum_{27 cells} sign_I grad w_I -- one gather per particle, no atomics, no
+ * scratch: bit-identical from run to run for one sign field.  x is the forward's.
+ * M < 1, T < 1, a null handle / x / targets / loss / work (fwd), a null x / sign / g_loss / g_x (bwd): UD_ERR_INVALID. */
+size_t ud_plb_density_seq_work_bytes(const ud_plb* h, long M);
+size_t ud_plb_density_seq_sign_bytes(const ud_plb* h, long M);
+int ud_plb_density_seq_fwd(ud_plb* h, long M, const double* x, const double* targets, int T, const int* target_index, double* loss,
+                           void* sign, void* work, size_t work_bytes, void* stream);
+int ud_plb_density_seq_bwd(ud_plb* h, long M, const double* x, const void* sign, const double* g_loss, double* g_x, void* stream);
+
+/* Chamfer distance of point clouds, the number an identification ends with (solver.py:187-196, scipy cdist), forward only, handle-free:
+ * a [M,Na,3]; b [Tb,Nb,3]; b_index [M] (device int32; NULL = cloud 0 for every item); out [M]:
+ *   out = mean_i min_j d(a_i, b_j) + mean_j min_i d(a_i, b_j),  d = sqrt((dx dx + dy dy) + dz dz), unfused.
+ * min_ab [M,Na], min_ba [M,Nb] (each may be NULL) receive the two sets of minima.  NaN propagates as np.min does.  The means are
+ * fixed-order sums: the same input gives the same bits, with or without the min arrays.  With both arrays given the minima are taken
+ * by ceil(Na / 256) + ceil(Nb / 256) workgroups per item (the design point, 10 000 x 10 000 points per item); otherwise by one
+ * workgroup per item.  Nothing of size Na x Nb is ever stored.  A b_index[m] outside [0, Tb) reads nothing out of bounds: out[m] and
+ * that item's minima are NaN.  M, Na, Nb, Tb < 1 or a null a / b / out: UD_ERR_INVALID. */
+int ud_plb_chamfer(long M, int Na, const double* a, int Tb, int Nb, const double* b, const int* b_index, double* out, double* min_ab,
+                   double* min_ba, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Cloth-env arithmetic either side of the rollout (the reference jit-fuses it into step_diff; here one forward and
  * one backward kernel per piece, one workgroup per env, instead of ~180 elementwise launches per step_diff).

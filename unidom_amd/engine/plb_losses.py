@@ -110,6 +110,46 @@ class PlbLoss:
                 "incremental_iou": incremental_iou_of(iou, self._init_iou, tiou)}
 
 
+class PlbTrajectoryLoss:
+    """The identification loss of PlasticineLab's sim2sim / real2sim trees (engine/losses/loss.py: new_target_density[f], update_target_density):
+    a recording is a sequence of target densities, one per env step, and a rollout is scored frame by frame against it, the density term
+    only.  All the frames of a rollout go through ONE PlbSimulator.density_seq_loss call."""
+
+    def __init__(self, sim):
+        self.sim = sim
+        self.targets = None      # [T,n,n,n]
+        self.n_frames = 0
+        self.per_env = False
+
+    def update_target_density(self, grids):
+        """grids: [K,n,n,n], one recording shared by the envs, or [B,K,n,n,n], one per env (array, tensor, or the path of a .npy)."""
+        if isinstance(grids, (str, bytes)) or hasattr(grids, "__fspath__"):
+            grids = np.load(grids, allow_pickle=True)
+        n, B = self.sim.n_grid, self.sim.batch_size
+        if not torch.is_tensor(grids):
+            grids = np.array(grids, dtype=np.float64)            # a copy, as the reference takes one
+        g = torch.as_tensor(grids, dtype=torch.float64, device=self.sim.device)
+        assert g.dim() in (4, 5) and tuple(g.shape[-3:]) == (n, n, n), tuple(g.shape)
+        self.per_env = g.dim() == 5
+        assert not self.per_env or g.shape[0] == B, (tuple(g.shape), B)
+        self.n_frames = int(g.shape[-4])
+        self.targets = g.detach().reshape(-1, n, n, n).contiguous().clone()
+        return self
+
+    def loss_of(self, states, frames):
+        """states: a list of PlbState (or of x tensors [B,N,3]); frames: the target frame of each.  Returns [len(states), B]."""
+        assert self.targets is not None, "update_target_density first"
+        frames = [int(f) for f in frames]
+        assert len(frames) == len(states) and all(0 <= f < self.n_frames for f in frames), (frames, self.n_frames)
+        x = torch.stack([s.x if hasattr(s, "x") else s for s in states])        # [L,B,N,3]
+        B = x.shape[1]
+        fr = torch.tensor(frames, dtype=torch.int32, device=self.sim.device)[:, None].expand(-1, B)
+        if self.per_env:
+            assert B == self.sim.batch_size
+            fr = fr + torch.arange(B, dtype=torch.int32, device=self.sim.device)[None] * self.n_frames
+        return self.sim.density_seq_loss(x, self.targets, fr.contiguous())
+
+
 def incremental_iou_of(iou, init_iou, target_iou):
     """incremental_iou of Loss.compute_loss (:294): clip((iou - init) / (target - init), 0, 1)."""
     return torch.clamp((iou - init_iou) / (target_iou - init_iou), 0.0, 1.0)

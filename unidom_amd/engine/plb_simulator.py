@@ -67,6 +67,33 @@ class PlbConf:
     action_dim = 3
     action_scale_w = (1.0, 1.0, 1.0)
     softness = 666.0         # Primitive cfg default, set_softness()
+    # True: the handle is created with the unit action scale and `step` applies action.clamp(-1, 1) * action_scale in torch (the kernel's own
+    # clip is then the identity; torch's clamp passes the cotangent at equality, as the header specifies) -- a Sphere handle with a scale
+    # thereby runs the persistent kernels (launch_plan() == 2).  Every |action_scale| must be <= 1.  Not with rot_state
+    action_scale_on_host = False
+
+
+class MoveConf(PlbConf):
+    """PlasticineLab/sim2sim/plb/envs/move.yml over sim2sim/plb/config/default_config.py, the env of the reference's identification runs:
+    a 1000-particle rod lying on the floor and one Sphere at its end, action.scale 0.005.  E and nu are default_config's (the file sets
+    neither).  The file's `mu` / `lam` entries (354.0, 2220.4) are read by nothing: mpm_simulator.py:26 takes cfg.E and cfg.nu, so they
+    are not mirrored here.  The scale is applied on the host, so the handle runs the persistent path."""
+    n_particles = 1000
+    E = 5e3
+    nu = 0.35
+    yield_stress = 1762.2
+    gravity = (0.0, -0.4, 0.0)
+    ground_friction = 0.5
+    box_width = (0.5, 0.028, 0.028)
+    box_init_pos = (0.5, 0.0125, 0.5)
+    prim_kind = (0,)
+    prim_radius = (0.025,)
+    prim_h = (0.0,)
+    prim_init_pos = ((0.745, 0.02, 0.5),)
+    prim_rot = ((1.0, 0.0, 0.0, 0.0),)
+    prim_friction = (0.0,)
+    action_scale = (0.005, 0.005, 0.005)
+    action_scale_on_host = True
 
 
 class WriterConf(PlbConf):
@@ -240,6 +267,36 @@ class _PlbLoss(torch.autograd.Function):
         return None, gx, gpp, None, None, None, None
 
 
+class _PlbDensitySeq(torch.autograd.Function):
+    """ud_plb_density_seq_fwd / _bwd: x [M,N,3], targets [T,G], index [M] int32 or None -> loss [M].  Keeps x and the sign field."""
+    @staticmethod
+    def forward(ctx, sim, x, targets, index, work_bytes):
+        L = _lib.lib()
+        x = _c(x)
+        M, dev = x.shape[0], x.device
+        loss = torch.empty((M,), dtype=torch.float64, device=dev)
+        sign = None
+        if ctx.needs_input_grad[1]:
+            sign = torch.empty((int(L.ud_plb_density_seq_sign_bytes(sim._h, M)) // 8,), dtype=torch.int64, device=dev)
+        nbytes = int(L.ud_plb_density_seq_work_bytes(sim._h, M)) if work_bytes is None else int(work_bytes)
+        work = torch.empty((max(nbytes // 8, 1),), dtype=torch.float64, device=dev)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(L.ud_plb_density_seq_fwd(sim._h, M, _p(x), _p(targets), int(targets.shape[0]), _p(index), _p(loss), _p(sign), _p(work),
+                                            nbytes, stream), "ud_plb_density_seq_fwd")
+        ctx.sim, ctx.M = sim, M
+        ctx.save_for_backward(x, sign)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gl):
+        x, sign = ctx.saved_tensors
+        gl = _c(gl)
+        gx = torch.empty_like(x)
+        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        _lib.check(_lib.lib().ud_plb_density_seq_bwd(ctx.sim._h, ctx.M, _p(x), _p(sign), _p(gl), _p(gx), stream), "ud_plb_density_seq_bwd")
+        return None, gx, None, None, None
+
+
 class PlbSimulator:
     def __init__(self, cfg=None, batch_size=1, device="cuda"):
         cfg = PlbConf() if cfg is None else cfg
@@ -262,6 +319,16 @@ class PlbSimulator:
         # where it fits), 1 = multi-kernel, 2 = persistent; lanes / sort_every: diagnostics of the multi-kernel path / the spatial order
         self.path, self.lanes, self.sort_every = (int(getattr(cfg, k, 0)) for k in ("path", "lanes", "sort_every"))
         P = self.n_primitive
+        # action_scale_on_host: the handle gets the unit scale, step() scales the clamped action in torch
+        self._host_scale = None
+        handle_scale = tuple(float(s) for s in cfg.action_scale)
+        if getattr(cfg, "action_scale_on_host", False):
+            if any(abs(s) > 1.0 for s in handle_scale):
+                raise ValueError(f"action_scale_on_host needs every |action_scale| <= 1 (the kernel clips the scaled action to [-1, 1]): {handle_scale}")
+            if getattr(cfg, "rot_state", False):
+                raise ValueError("action_scale_on_host is not available on a rot_state handle")
+            self._host_scale = torch.tensor(handle_scale, dtype=torch.float64, device=self.device)
+            handle_scale = (1.0, 1.0, 1.0)
         pad = lambda seq, fill: (list(seq)[:P] + [fill] * 2)[:2]
         self.prim_kind = tuple(int(k) for k in pad(cfg.prim_kind, 0))[:P]
         self.rot_state = bool(getattr(cfg, "rot_state", False))
@@ -274,7 +341,7 @@ class PlbSimulator:
             lower_bound=(C.c_double * 3)(*cfg.lower_bound), upper_bound=(C.c_double * 3)(*cfg.upper_bound),
             grid_ckpt_cells=int(self.grid_ckpt_cells), max_envs=int(batch_size), path=self.path, lanes=self.lanes, sort_every=self.sort_every,
             prim_kind=(C.c_int * 2)(*pad(cfg.prim_kind, 0)), capsule_h=(C.c_double * 2)(*pad(cfg.prim_h, 0.0)), prim_rot=rot,
-            prim_friction=(C.c_double * 2)(*pad(cfg.prim_friction, 0.0)), action_scale=(C.c_double * 3)(*cfg.action_scale),
+            prim_friction=(C.c_double * 2)(*pad(cfg.prim_friction, 0.0)), action_scale=(C.c_double * 3)(*handle_scale),
             rot_state=int(self.rot_state), action_dim=int(getattr(cfg, "action_dim", 3)),
             action_scale_w=(C.c_double * 3)(*getattr(cfg, "action_scale_w", (1.0, 1.0, 1.0))))
         self._h = C.c_void_p()
@@ -344,6 +411,8 @@ class PlbSimulator:
                                                        action, state.E, state.nu, state.yield_stress)
             return state._replace(x=xo, v=vo, C=Co, F=Fo, prim_pos=po, prim_rot=ro)
         action = torch.as_tensor(action, dtype=torch.float64, device=self.device).reshape(B, 3)
+        if self._host_scale is not None:
+            action = action.clamp(-1.0, 1.0) * self._host_scale
         xo, vo, Co, Fo, po = _PlbStep.apply(self, state.x, state.v, state.C, state.F, state.prim_pos, state.softness, action,
                                             state.E, state.nu, state.yield_stress)
         return state._replace(x=xo, v=vo, C=Co, F=Fo, prim_pos=po)
@@ -368,6 +437,51 @@ class PlbSimulator:
         stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
         _lib.check(_lib.lib().ud_plb_grid_mass(self._h, C.c_int(B), _p(x), _p(gm), stream), "ud_plb_grid_mass")
         return gm
+
+    def density_seq_loss(self, x, targets, index=None, work_bytes=None):
+        """The identification loss of a sequence of clouds (sim2sim / real2sim compute_loss with new_target_density[f]; ud_plb_density_seq_*):
+        x [..., N, 3]; targets [T, n, n, n]; index: the target of every cloud, x's leading shape (None = target 0).  Returns
+        sum_I |grid_mass(x)_I - targets[index]_I| in x's leading shape, differentiable in x.  The number of clouds is not bound by
+        batch_size.  An index outside [0, T) gives NaN and no gradient.  work_bytes: the scratch of the forward (None = the library's
+        choice); it is taken in chunks of work_bytes / (8 n^3) clouds."""
+        n, N = self.n_grid, self.n_particles
+        assert x.shape[-2:] == (N, 3), tuple(x.shape)
+        lead = tuple(x.shape[:-2])
+        td = torch.as_tensor(targets, dtype=torch.float64, device=self.device)
+        assert td.dim() == 4 and tuple(td.shape[1:]) == (n, n, n), tuple(td.shape)
+        td = td.detach().reshape(td.shape[0], -1).contiguous()
+        xf = x.reshape(-1, N, 3)
+        idx = None
+        if index is not None:
+            idx = torch.as_tensor(index, device=self.device).to(torch.int32).reshape(-1).contiguous()
+            assert idx.numel() == xf.shape[0], (tuple(idx.shape), lead)
+        return _PlbDensitySeq.apply(self, xf, td, idx, work_bytes).reshape(lead)
+
+    def chamfer(self, a, b, index=None, return_mins=False):
+        """Chamfer distance (solver.py:187-196; ud_plb_chamfer): a [..., Na, 3]; b [Nb, 3] or [Tb, Nb, 3]; index: the cloud of b every cloud of a is
+        held against (None = cloud 0).  mean_i min_j |a_i - b_j| + mean_j min_i |a_i - b_j| in a's leading shape; no gradient.
+        return_mins: also the two sets of minima [..., Na] and [..., Nb]."""
+        a = torch.as_tensor(a, dtype=torch.float64, device=self.device).detach()
+        b = torch.as_tensor(b, dtype=torch.float64, device=self.device).detach()
+        if b.dim() == 2:
+            b = b[None]
+        assert a.shape[-1] == 3 and b.dim() == 3 and b.shape[-1] == 3, (tuple(a.shape), tuple(b.shape))
+        lead, Na, (Tb, Nb) = tuple(a.shape[:-2]), a.shape[-2], b.shape[:2]
+        af, b = a.reshape(-1, Na, 3).contiguous(), b.contiguous()
+        M = af.shape[0]
+        idx = None
+        if index is not None:
+            idx = torch.as_tensor(index, device=self.device).to(torch.int32).reshape(-1).contiguous()
+            assert idx.numel() == M
+        out = torch.empty((M,), dtype=torch.float64, device=self.device)
+        # always given: with both arrays the minima are taken by many workgroups per item (include/unidom_hip.h)
+        mab = torch.empty((M, Na), dtype=torch.float64, device=self.device)
+        mba = torch.empty((M, Nb), dtype=torch.float64, device=self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(_lib.lib().ud_plb_chamfer(M, int(Na), _p(af), int(Tb), int(Nb), _p(b), _p(idx), _p(out), _p(mab), _p(mba), stream), "ud_plb_chamfer")
+        if return_mins:
+            return out.reshape(lead), mab.reshape(lead + (Na,)), mba.reshape(lead + (Nb,))
+        return out.reshape(lead)
 
     @staticmethod
     def set_softness1(state: PlbState, softness) -> PlbState:   # primitives.py: Primitives.set_softness1
