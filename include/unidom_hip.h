@@ -520,6 +520,37 @@ int ud_plb_density_seq_bwd(ud_plb* h, long M, const double* x, const void* sign,
 int ud_plb_chamfer(long M, int Na, const double* a, int Tb, int Nb, const double* b, const int* b_index, double* out, double* min_ab,
                    double* min_ba, void* stream);
 
+/* Closed-loop policy (GenORM policy/pbm/plb/engine/nn/mlp.py:63-127, driven by optimizer/solver_nn.py:28-43): the reference's MLP over a
+ * strided sample of the particle state and every primitive's pose, for B envs, float64, handle-free (csrc/plb_policy.hip).  Launches
+ * only: no allocation, no synchronisation, no atomics, capturable in a HIP graph; two runs give the same bits.
+ *   dims (host, n_layer + 1 ints) = d_0 .. d_L;  d_0 = 6 obs_num + 7 P;  d_L = the action dimension.
+ *   observation h_0[b] (mlp.py:68-86): for i < obs_num: x[b, i obs_step, 0..2], then v[b, i obs_step, 0..2] * velocity_weight; then per
+ *     primitive prim_pos[b,p,0..2], prim_rot[b,p,0..3] (w, x, y, z).  x, v [B,N,3]; prim_pos [B,P,3]; prim_rot [B,P,4].
+ *   layers (mlp.py:111-125): h_{l+1} = act(W_l h_l + b_l), W_l [d_{l+1}, d_l] row-major; activation 0 = relu, 1 = tanh on the hidden
+ *     layers, none on the last.   action [B, d_L] = clamp(h_L, -1, 1) (mlp.py:92-99).
+ *   params (get_params, mlp.py:161-166): W_0, b_0, W_1, b_1, ... flat, ud_plb_policy_n_params(n_layer, dims) doubles; env b reads
+ *     params + b * param_stride: n_params (or more) for B policies side by side, 0 for one policy shared by every env.
+ *   velocity_weight (mlp.py:44, needs_grad=False) is a plain argument and is not differentiated.
+ *   tape: ud_plb_policy_tape_bytes(B, n_layer, dims) bytes, opaque (every layer's output and d_1 words per env that the backward hands
+ *     from its first launch to its second: the backward WRITES those, so two backward calls on one tape must not run concurrently; one
+ *     after the other they are independent).  NULL in the forward = no backward follows; the action has the same bits either way.
+ * ud_plb_policy_bwd: given g_action [B, d_L] writes g_x, g_v [B,N,3] in full (zero at unobserved particles, g_v carrying
+ *   velocity_weight), g_prim_pos [B,P,3], g_prim_rot [B,P,4], and ADDS the parameter gradient to g_params [B, n_params] (one row per
+ *   env also with param_stride 0; the caller zeroes it: Taichi's W.grad / b.grad, get_grad mlp.py:154-159).  The clamp passes the
+ *   cotangent where |h_L| <= 1, equality included; relu passes it where the output is > 0.  params are the forward's.
+ * Limits: n_layer in [1, 4] (0 to 3 hidden layers); d_1 .. d_L in [1, 1024]; d_0 in [1, 4096]; B in [1, 65535]; P in [0, 64].
+ * UD_ERR_INVALID, with nothing launched: n_layer or a width outside those limits, dims[0] != 6 obs_num + 7 P, obs_step < 1,
+ * (obs_num - 1) obs_step >= N, activation not 0 / 1, a null array, 0 < param_stride < n_params.  The two size calls return 0 for
+ * n_layer outside the limits or a width below 1. */
+size_t ud_plb_policy_n_params(int n_layer, const int* dims);
+size_t ud_plb_policy_tape_bytes(int B, int n_layer, const int* dims);
+int ud_plb_policy_fwd(int B, int N, int P, int obs_step, int obs_num, int n_layer, const int* dims, int activation, double velocity_weight,
+                      const double* x, const double* v, const double* prim_pos, const double* prim_rot, const double* params,
+                      long param_stride, double* action, void* tape, void* stream);
+int ud_plb_policy_bwd(int B, int N, int P, int obs_step, int obs_num, int n_layer, const int* dims, int activation, double velocity_weight,
+                      const double* params, long param_stride, void* tape, const double* g_action, double* g_x, double* g_v,
+                      double* g_prim_pos, double* g_prim_rot, double* g_params, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Cloth-env arithmetic either side of the rollout (the reference jit-fuses it into step_diff; here one forward and
  * one backward kernel per piece, one workgroup per env, instead of ~180 elementwise launches per step_diff).

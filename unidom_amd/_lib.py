@@ -23,6 +23,7 @@ SYMBOLS = [
     "ud_plb_step_fwd_rot", "ud_plb_step_bwd_rot", "ud_plb_loss_fwd_rot", "ud_plb_loss_bwd_rot",
     "ud_plb_grid_mass", "ud_plb_target_work_bytes", "ud_plb_target_sdf", "ud_plb_density_iou_work_bytes", "ud_plb_density_iou",
     "ud_plb_density_seq_work_bytes", "ud_plb_density_seq_sign_bytes", "ud_plb_density_seq_fwd", "ud_plb_density_seq_bwd", "ud_plb_chamfer",
+    "ud_plb_policy_n_params", "ud_plb_policy_tape_bytes", "ud_plb_policy_fwd", "ud_plb_policy_bwd",
     "ud_chamfer_fwd", "ud_chamfer_bwd", "ud_cloth_pnp_fwd", "ud_cloth_pnp_bwd", "ud_cloth_depth_fwd", "ud_cloth_depth_bwd",
     "ud_mpm_focus_fwd", "ud_mpm_focus_bwd", "ud_mpm_finish_fwd", "ud_mpm_finish_bwd",
 ]
@@ -93,6 +94,8 @@ def lib():
         L.ud_plb_density_iou_work_bytes.restype = C.c_size_t
         L.ud_plb_density_seq_work_bytes.restype = C.c_size_t
         L.ud_plb_density_seq_sign_bytes.restype = C.c_size_t
+        L.ud_plb_policy_n_params.restype = C.c_size_t
+        L.ud_plb_policy_tape_bytes.restype = C.c_size_t
         for name in SYMBOLS:
             if not hasattr(L, name):
                 raise UnidomError(f"{SO_PATH} does not export {name}")
@@ -108,6 +111,11 @@ def lib():
         L.ud_plb_density_seq_fwd.argtypes = [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]
         L.ud_plb_density_seq_bwd.argtypes = [C.c_void_p, C.c_long] + [C.c_void_p] * 5
         L.ud_plb_chamfer.argtypes = [C.c_long, C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6
+        L.ud_plb_policy_n_params.argtypes = [C.c_int, C.c_void_p]
+        L.ud_plb_policy_tape_bytes.argtypes = [C.c_int, C.c_int, C.c_void_p]
+        shape = [C.c_int] * 6 + [C.c_void_p, C.c_int, C.c_double]     # B N P obs_step obs_num n_layer dims activation velocity_weight
+        L.ud_plb_policy_fwd.argtypes = shape + [C.c_void_p] * 5 + [C.c_long] + [C.c_void_p] * 3
+        L.ud_plb_policy_bwd.argtypes = shape + [C.c_void_p, C.c_long] + [C.c_void_p] * 8
         _LIB = L
     return _LIB
 
