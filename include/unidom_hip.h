@@ -551,6 +551,40 @@ int ud_plb_policy_bwd(int B, int N, int P, int obs_step, int obs_num, int n_laye
                       const double* params, long param_stride, void* tape, const double* g_action, double* g_x, double* g_v,
                       double* g_prim_pos, double* g_prim_rot, double* g_params, void* stream);
 
+/* Point-cloud policy (GenORM policy/pnet2_layers with tf_ops/sampling/tf_sampling_g.cu and tf_ops/grouping/tf_grouping_g.cu): the
+ * sampling and grouping ops of the PointNet++ single-scale-grouping model, float32, handle-free (csrc/pc_group.hip).  Launches only: no
+ * allocation, no synchronisation, no environment variable, no atomics, capturable in a HIP graph; two runs give the same bits.  Indices
+ * are int32.  Every input is finite: a NaN (or an overflowing distance that turns into one) is outside the contract.  B in [1, 65535].
+ *
+ * ud_pc_fps: farthest-point sampling and the gather_point that follows it, one launch.  xyz [B,n,3] -> idx [B,m], new_xyz [B,m,3] =
+ *   xyz[b, idx[b,j]].  idx[b,0] = 0; with mind[k] = 1e38f at the start, sample j updates mind[k] = min(mind[k], d(k, sample j-1)) and
+ *   takes the arg-max of mind, d = (dx dx + dy dy) + dz dz unfused.  TIE RULE: the lowest index among the maxima.  That is the
+ *   reference's block reduction for n <= 512 (every cloud the policy feeds it); for larger n the reference breaks ties by
+ *   (k mod 512, k), which this call does not reproduce.  The deviation shows only on exact f32 ties between different points; tied
+ *   duplicates have equal coordinates, so new_xyz is the same.  m > n is legal (the policy samples 512 of 200): once every mind is 0
+ *   index 0 repeats.  n in [1, 8192] (above: UD_ERR_UNSUPPORTED), m >= 1.  n <= 256 runs one wave per cloud, larger n one workgroup.
+ * ud_pc_ball_query: xyz [B,n,3], new_xyz [B,m,3] -> idx [B,m,nsample], cnt [B,m].  Row (b,j) = the first nsample indices k, ascending,
+ *   with fmaxf(sqrtf((dx dx + dy dy) + dz dz), 1e-20f) < radius (strict; the correctly rounded sqrt, not s < r r); the remaining slots
+ *   repeat the first hit; cnt = the number of hits, at most nsample.  A centre without a hit gets a row of zeros and cnt 0 (the
+ *   reference leaves that row uninitialised).
+ * ud_pc_group_fwd: sample_and_group's group, recentre and concat (pnet2_layers/utils.py:26-31), xyz first:
+ *   out [B,m,nsample,3+C]: out[b,j,k,:3] = xyz[b,idx[b,j,k]] - new_xyz[b,j], out[b,j,k,3:] = feats[b,idx[b,j,k]].  feats [B,n,C], NULL
+ *   with C = 0.  An index outside [0, n) reads nothing and gives a row of zeros.
+ * ud_pc_group_bwd: its adjoint; every output is WRITTEN in full (nothing is added to).  g_new_xyz[b,j] = -(sum_k g_out[b,j,k,:3]), k
+ *   ascending from +0; g_xyz[b,i] / g_feats[b,i] = the sum of g_out[b,j,k,:3] / [3:] over the (j,k) with idx[b,j,k] = i, in ascending
+ *   (j,k) from +0 (an index outside [0, n) adds to nothing).  centre_idx [B,m] (the FPS indices; NULL = new_xyz is an independent
+ *   input): g_new_xyz[b,j] is then added into g_xyz[b, centre_idx[b,j]], ascending j, after the sums above.  g_feats may be NULL
+ *   with C = 0.  No scratch.
+ * m nsample (3 + C) < 2^31 - 256 for the two group calls (UD_ERR_UNSUPPORTED above).  A size below 1, C < 0 or a null array:
+ * UD_ERR_INVALID.  Nothing is launched on an error. */
+int ud_pc_fps(int B, int n, int m, const float* xyz, int* idx, float* new_xyz, void* stream);
+int ud_pc_ball_query(int B, int n, int m, float radius, int nsample, const float* xyz, const float* new_xyz, int* idx, int* cnt,
+                     void* stream);
+int ud_pc_group_fwd(int B, int n, int m, int nsample, int C, const float* xyz, const float* feats, const float* new_xyz, const int* idx,
+                    float* out, void* stream);
+int ud_pc_group_bwd(int B, int n, int m, int nsample, int C, const int* idx, const int* centre_idx, const float* g_out, float* g_xyz,
+                    float* g_feats, float* g_new_xyz, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Cloth-env arithmetic either side of the rollout (the reference jit-fuses it into step_diff; here one forward and
  * one backward kernel per piece, one workgroup per env, instead of ~180 elementwise launches per step_diff).

@@ -24,6 +24,7 @@ SYMBOLS = [
     "ud_plb_grid_mass", "ud_plb_target_work_bytes", "ud_plb_target_sdf", "ud_plb_density_iou_work_bytes", "ud_plb_density_iou",
     "ud_plb_density_seq_work_bytes", "ud_plb_density_seq_sign_bytes", "ud_plb_density_seq_fwd", "ud_plb_density_seq_bwd", "ud_plb_chamfer",
     "ud_plb_policy_n_params", "ud_plb_policy_tape_bytes", "ud_plb_policy_fwd", "ud_plb_policy_bwd",
+    "ud_pc_fps", "ud_pc_ball_query", "ud_pc_group_fwd", "ud_pc_group_bwd",
     "ud_chamfer_fwd", "ud_chamfer_bwd", "ud_cloth_pnp_fwd", "ud_cloth_pnp_bwd", "ud_cloth_depth_fwd", "ud_cloth_depth_bwd",
     "ud_mpm_focus_fwd", "ud_mpm_focus_bwd", "ud_mpm_finish_fwd", "ud_mpm_finish_bwd",
 ]
@@ -116,6 +117,10 @@ def lib():
         shape = [C.c_int] * 6 + [C.c_void_p, C.c_int, C.c_double]     # B N P obs_step obs_num n_layer dims activation velocity_weight
         L.ud_plb_policy_fwd.argtypes = shape + [C.c_void_p] * 5 + [C.c_long] + [C.c_void_p] * 3
         L.ud_plb_policy_bwd.argtypes = shape + [C.c_void_p, C.c_long] + [C.c_void_p] * 8
+        L.ud_pc_fps.argtypes = [C.c_int] * 3 + [C.c_void_p] * 4
+        L.ud_pc_ball_query.argtypes = [C.c_int] * 3 + [C.c_float, C.c_int] + [C.c_void_p] * 5
+        L.ud_pc_group_fwd.argtypes = [C.c_int] * 5 + [C.c_void_p] * 6
+        L.ud_pc_group_bwd.argtypes = [C.c_int] * 5 + [C.c_void_p] * 7
         _LIB = L
     return _LIB
 
