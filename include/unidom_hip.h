@@ -318,6 +318,17 @@ int ud_mpm_step_bwd(ud_mpm* h, int B, const void* ckpt, const float* prim_size, 
  * D, influence, cv) and P_{f+1}; orientation, height, radius, friction and softness are not leaves.  The contact loss takes the
  * Capsule's distance.  Without rot_state the orientation is a handle constant (only primitive 0 is actuated, three action dimensions).
  * A handle with a Capsule, or with an action_scale other than (1, 1, 1), runs the multi-kernel path only.
+ * 3 Box, 4 Cylinder, 5 Torus (primitives.py:241-269, 176-202, 211-231): the same contact model, with the kind's own _sdf / _normal of the
+ * local point pl in place of the Capsule's; length(x) = sqrt(x.x + 1e-14) everywhere.  Box (prim_shape = size, three half extents):
+ * q = |pl| - size, sdf = length(max(q, 0)) + min(max(q0, q1, q2), 0); the normal is the reference's central difference of that sdf,
+ * n_i = (0.5 / d)(sdf(pl + d e_i) - sdf(pl - d e_i)) with d = 1e-4, normalised -- not an analytic normal.  Cylinder (prim_shape = (h, r):
+ * h the radial half extent, r the axial one): d = (length((pl.x, pl.z)) - h, |pl.y| - r), sdf = min(max(d0, d1), 0) + length(max(d, 0)),
+ * normal from n2 = max(d, 0) + [max(d0, d1) <= 0] ([d0 > d1], 1 - [d0 > d1]) normalised, spread over (pl.x, pl.z) / l and the sign
+ * [pl.y >= 0] 2 - 1, normalised again.  Torus (prim_shape = (tx, ty)): q = (length((pl.x, pl.z)) - tx, pl.y), sdf = length(q) - ty,
+ * normal (x / l q0 / |q|, q1 / |q|, z / l q0 / |q|) normalised.  Their adjoints hold indicators, signs and the arm abs / min / max took
+ * constant (sub-gradients at ties are unspecified); the Box normal's adjoint is the exact derivative of the finite-difference formula (the
+ * analytic sdf gradient at the six sample points), not that of a true box normal.  Shape constants are not leaves.  Such a handle runs
+ * kernels of its own on the multi-kernel path; a Capsule may sit beside a new shape.  Specification: tests/plb_shape_twin.py.
  * Rotating primitives (rot_state; the *_rot entry points).  Every primitive carries a rotation (w, x, y, z) beside its position, as the
  * reference's Primitive does (primive_base.py:31-38), turned once per substep (:117-121):
  *   a = clip(action, -1, 1) (its cotangent passes at equality and is zero outside);
@@ -370,19 +381,22 @@ typedef struct {
                             call and every sort_every-th forward call after it; 0 = 8; negative = never */
   /* Everything below: zero = the handle of before these fields existed (sticky Spheres, action scale 1) */
   int prim_kind[2];      /* 0 sticky Sphere, 1 Capsule (radius[i], capsule_h[i], prim_rot[i], prim_friction[i]), 2 RollingPin (the Capsule's
-                            geometry, its own kinematics; needs rot_state and three action dimensions); else UD_ERR_INVALID.  A handle
-                            with a Capsule runs the multi-kernel path (path = 0 picks it; path = 2: UD_ERR_UNSUPPORTED) */
+                            geometry, its own kinematics; needs rot_state and three action dimensions), 3 Box, 4 Cylinder, 5 Torus
+                            (prim_shape[i], prim_rot[i], prim_friction[i]; radius[i] and capsule_h[i] are ignored); else UD_ERR_INVALID.
+                            A handle with any kind but 0 runs the multi-kernel path (path = 0 picks it; path = 2: UD_ERR_UNSUPPORTED) */
   double capsule_h[2];   /* Capsule: length of the axis segment (along the primitive's y), >= 0; radius[i] > 0 */
   double prim_rot[2][4]; /* Capsule: constant orientation (w, x, y, z); all four zero = identity, else |q| > 0.9 as the reference asserts */
   double prim_friction[2];   /* Capsule: Coulomb friction of the contact (primitive cfg.friction) */
   double action_scale[3];    /* primitive 0: v = clip(action, -1, 1) * action_scale / substeps (set_velocity); all zero = (1, 1, 1).  Any
                                 other value: multi-kernel path, as with a Capsule */
   int rot_state;             /* nonzero: every primitive's orientation is per-env state, passed through the *_rot entry points (prim_rot above is
-                                then unused by the kernels).  Primitive 0 must be kind 1 or 2, primitive 1 (unactuated, never moves) a sticky
+                                then unused by the kernels).  Primitive 0 must be kind 1 to 5, primitive 1 (unactuated, never moves) a sticky
                                 Sphere: anything else, and path = 2, UD_ERR_UNSUPPORTED */
   int action_dim;            /* 0 or 3: three action dimensions.  6: (v, w) of the base class (set_velocity, primive_base.py:185-193); needs
                                 rot_state (UD_ERR_INVALID without) */
   double action_scale_w[3];  /* action.scale[3:6]: w = clip(action[3:6], -1, 1) * action_scale_w / substeps; all zero = (1, 1, 1) */
+  double prim_shape[2][3];   /* kinds 3 to 5: Box size (three half extents), Cylinder (h, r, -), Torus (tx, ty, -); a used constant <= 0 is
+                                UD_ERR_INVALID.  Kinds 0 to 2 ignore it (zero = the handle of before) */
 } ud_plb_conf;
 
 int ud_plb_create(const ud_plb_conf* conf, ud_plb** out);

@@ -58,7 +58,8 @@ class ud_plb_conf(C.Structure):
                 ("grid_ckpt_cells", C.c_int), ("max_envs", C.c_int), ("path", C.c_int), ("lanes", C.c_int), ("sort_every", C.c_int),
                 ("prim_kind", C.c_int * 2), ("capsule_h", C.c_double * 2), ("prim_rot", (C.c_double * 4) * 2),
                 ("prim_friction", C.c_double * 2), ("action_scale", C.c_double * 3),
-                ("rot_state", C.c_int), ("action_dim", C.c_int), ("action_scale_w", C.c_double * 3)]
+                ("rot_state", C.c_int), ("action_dim", C.c_int), ("action_scale_w", C.c_double * 3),
+                ("prim_shape", (C.c_double * 3) * 2)]
 
 
 def build(force: bool = False) -> str:

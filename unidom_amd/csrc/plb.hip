@@ -162,7 +162,7 @@ __global__ void __launch_bounds__(256) plb_p2g(PlbArgs a) {
 }
 
 // grid_op (:200-232) over the touched cells.  GEN: the handle has a general primitive (plb_prim.h), fixed at create
-template <int GEN>   // 2: a rot_state handle, the substep's two quaternions per primitive read from the rotation trajectory
+template <int GEN>   // 2: a rot_state handle, the substep's two quaternions per primitive read from the rotation trajectory; 3 / 4: a shape handle without / with it
 __global__ void __launch_bounds__(256) plb_grid(PlbArgs a, PlbPrimArg<GEN> pr) {
   const int b = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x;
   const PlbConst& c = a.c;
@@ -184,7 +184,7 @@ __global__ void __launch_bounds__(256) plb_grid(PlbArgs a, PlbPrimArg<GEN> pr) {
     o[0] = cell[0]; o[1] = cell[1]; o[2] = cell[2]; o[3] = cell[3];
   }
   double vv[3];
-  if constexpr (GEN == 2) plb_grid_cell_any<GEN>(c, pr, lin, cell[0], cell + 1, a.w.pos + ((long)b * (c.S + 1) + a.f) * c.np * 3, a.softness + b * c.np, vv,
+  if constexpr (GEN == 2 || GEN == 4) plb_grid_cell_any<GEN>(c, pr, lin, cell[0], cell + 1, a.w.pos + ((long)b * (c.S + 1) + a.f) * c.np * 3, a.softness + b * c.np, vv,
                                                  pr.r.rot + ((long)b * (c.S + 1) + a.f) * c.np * 4);
   else
   plb_grid_cell_any<GEN>(c, pr, lin, cell[0], cell + 1, a.w.pos + ((long)b * (c.S + 1) + a.f) * c.np * 3, a.softness + b * c.np, vv);
@@ -585,10 +585,10 @@ int ud_plb_create(const ud_plb_conf* conf, ud_plb** out) {
   }
   for (int pi = 0; pi < c.np; ++pi) {
     const int kind = conf->prim_kind[pi];
-    if (kind != 0 && kind != 1 && kind != 2) { ud::set_error("ud_plb_create: prim_kind[%d] = %d (0 Sphere, 1 Capsule, 2 RollingPin)", pi, kind); delete h; return UD_ERR_INVALID; }
+    if (kind < 0 || kind > 5) { ud::set_error("ud_plb_create: prim_kind[%d] = %d (0 Sphere, 1 Capsule, 2 RollingPin, 3 Box, 4 Cylinder, 5 Torus)", pi, kind); delete h; return UD_ERR_INVALID; }
     if (kind == 2 && !h->rot_state) { ud::set_error("ud_plb_create: prim_kind[%d] = 2 (RollingPin) requires rot_state", pi); delete h; return UD_ERR_INVALID; }
     if (h->rot_state) {
-      if (pi == 0 && kind == 0) { ud::set_error("ud_plb_create: rot_state: primitive 0 must be a Capsule (1) or a RollingPin (2), not a sticky Sphere"); delete h; return UD_ERR_UNSUPPORTED; }
+      if (pi == 0 && kind == 0) { ud::set_error("ud_plb_create: rot_state: primitive 0 must be a Capsule (1), a RollingPin (2), a Box (3), a Cylinder (4) or a Torus (5), not a sticky Sphere"); delete h; return UD_ERR_UNSUPPORTED; }
       if (pi == 1 && kind != 0) { ud::set_error("ud_plb_create: rot_state: primitive 1 is unactuated and must be a sticky Sphere (prim_kind[1] = %d)", kind); delete h; return UD_ERR_UNSUPPORTED; }
       if (kind == 2 && h->rot.adim != 3) { ud::set_error("ud_plb_create: the RollingPin takes three action dimensions (dw, dth, dy), action_dim = %d", conf->action_dim); delete h; return UD_ERR_UNSUPPORTED; }
       if (kind == 2) h->rot.kin = 2;
@@ -601,6 +601,20 @@ int ud_plb_create(const ud_plb_conf* conf, ud_plb** out) {
     if (kind != 0) {
       h->gen = true;
       if (!h->rot_state && !ident && !(std::sqrt(n2) > 0.9)) { ud::set_error("ud_plb_create: |prim_rot[%d]| = %g (the reference asserts > 0.9; all zero = identity)", pi, std::sqrt(n2)); delete h; return UD_ERR_INVALID; }
+    }
+    if (kind >= 3) {      // Box: size; Cylinder: (h, r); Torus: (tx, ty) -- radius[pi] and capsule_h[pi] are ignored
+      h->shape = true;
+      const int used = kind == 3 ? 3 : 2;
+      for (int k = 0; k < 3; ++k) {
+        const double sc = conf->prim_shape[pi][k];
+        if (k < used && !(sc > 0)) {
+          ud::set_error("ud_plb_create: prim_shape[%d][%d] = %g: a %s needs %s > 0", pi, k, sc, kind == 3 ? "Box" : kind == 4 ? "Cylinder" : "Torus",
+                        kind == 3 ? "its three half extents" : kind == 4 ? "(h, r)" : "(tx, ty)");
+          delete h; return UD_ERR_INVALID;
+        }
+        h->shp.c[pi][k] = k < used ? sc : 0.0;
+      }
+    } else if (kind != 0) {
       if (!(conf->capsule_h[pi] >= 0) || !(conf->radius[pi] > 0)) {
         ud::set_error("ud_plb_create: Capsule %d needs capsule_h >= 0 and radius > 0 (h = %g, r = %g)", pi, conf->capsule_h[pi], conf->radius[pi]); delete h; return UD_ERR_INVALID;
       }
@@ -615,7 +629,7 @@ int ud_plb_create(const ud_plb_conf* conf, ud_plb** out) {
   const bool mk_only = h->gen || !unit_scale;
   if (conf->path == 2 && mk_only) {
     ud::set_error("ud_plb_create: path = 2 (persistent) has no %s: such a handle runs the multi-kernel path (path = 0 or 1)",
-                  h->rot_state ? "rotating primitives (rot_state)" : h->gen ? "Capsule primitive (prim_kind = 1)" : "action_scale other than (1, 1, 1)");
+                  h->rot_state ? "rotating primitives (rot_state)" : h->shape ? "Box, Cylinder or Torus primitive (prim_kind = 3, 4, 5)" : h->gen ? "Capsule primitive (prim_kind = 1)" : "action_scale other than (1, 1, 1)");
     delete h; return UD_ERR_UNSUPPORTED;
   }
   h->G = (long)c.n_grid * c.n_grid * c.n_grid;
@@ -736,7 +750,9 @@ static int plb_step_fwd_impl(const char* who, ud_plb* h, int B, const double* x,
   UD_PLB_LAUNCH(plb_p2g);
   for (int f = 0; f < S; ++f) {
     set(f);
-    if (rot) hipLaunchKernelGGL(ud::plb_grid<2>, gc, blk, 0, st, a, ud::PlbPrimArg<2>{h->prim, rr});
+    if (rot && h->shape) hipLaunchKernelGGL(ud::plb_grid<4>, gc, blk, 0, st, a, ud::PlbPrimArg<4>{h->prim, rr, h->shp});
+    else if (h->shape) hipLaunchKernelGGL(ud::plb_grid<3>, gc, blk, 0, st, a, ud::PlbPrimArg<3>{h->prim, h->shp});
+    else if (rot) hipLaunchKernelGGL(ud::plb_grid<2>, gc, blk, 0, st, a, ud::PlbPrimArg<2>{h->prim, rr});
     else if (h->gen) hipLaunchKernelGGL(ud::plb_grid<1>, gc, blk, 0, st, a, ud::PlbPrimArg<1>{h->prim});
     else hipLaunchKernelGGL(ud::plb_grid<0>, gc, blk, 0, st, a, ud::PlbPrimArg<0>{});
     if (fused && f + 1 < S) {

@@ -25,7 +25,8 @@
 namespace ud {
 
 // ---- grid op, kept: v_out of every touched cell into buffer 1 (buffer 0 keeps (m, mv)) ---------------------------------
-template <int GEN>   // 1: the handle has a general primitive (plb_prim.h); 2: a rot_state handle, the substep's quaternions read from pr.r.rot
+template <int GEN>   // 1: the handle has a general primitive (plb_prim.h); 2: a rot_state handle, the substep's quaternions read from pr.r.rot;
+                     // 3 / 4: a shape handle (Box, Cylinder, Torus) without / with rot_state
 __global__ void __launch_bounds__(256) plb_grid_keep(PlbArgs a, PlbPrimArg<GEN> pr) {
   const int b = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x;
   const PlbConst& c = a.c;
@@ -58,7 +59,7 @@ __global__ void __launch_bounds__(256) plb_grid_keep(PlbArgs a, PlbPrimArg<GEN> 
     cell = plb_buf(a, cur, b) + lin * 4;
   }
   double vv[3];
-  if constexpr (GEN == 2) plb_grid_cell_any<GEN>(c, pr, lin, cell[0], cell + 1, a.w.pos + ((long)b * (c.S + 1) + a.f) * c.np * 3, a.softness + b * c.np, vv,
+  if constexpr (GEN == 2 || GEN == 4) plb_grid_cell_any<GEN>(c, pr, lin, cell[0], cell + 1, a.w.pos + ((long)b * (c.S + 1) + a.f) * c.np * 3, a.softness + b * c.np, vv,
                                                  pr.r.rot + ((long)b * (c.S + 1) + a.f) * c.np * 4);
   else
   plb_grid_cell_any<GEN>(c, pr, lin, cell[0], cell + 1, a.w.pos + ((long)b * (c.S + 1) + a.f) * c.np * 3, a.softness + b * c.np, vv);
@@ -181,7 +182,7 @@ __global__ void __launch_bounds__(256) plb_g2p_adj(PlbArgs a, int gs_in) {
 // ---- grid op adjoint (:200-232 in reverse), one touched cell per lane -------------------------------------------------
 template <int GEN>
 __global__ void __launch_bounds__(256) plb_grid_adj(PlbArgs a, PlbPrimArg<GEN> pr) {
-  constexpr bool ROT = GEN == 2;
+  constexpr bool ROT = GEN == 2 || GEN == 4;
   const int b = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x;
   const PlbConst& c = a.c;
   // per-env cotangents (sticky-sphere positions, ground friction): summed over the wave, one atomic per wave and word -- one per cell
@@ -196,6 +197,11 @@ __global__ void __launch_bounds__(256) plb_grid_adj(PlbArgs a, PlbPrimArg<GEN> p
   if (inlist) {
     const double g[3] = {ga[0], ga[1], ga[2]};
     double gout[4];
+    if constexpr (GEN == 4) plb_grid_cell_adj_gen<true, true>(c, pr.p, lin, cell[0], cell + 1, g, a.w.pos + ((long)b * (c.S + 1) + a.f) * c.np * 3, a.softness + b * c.np, gout, q0, qs, gfric,
+                                                              pr.r.rot + ((long)b * (c.S + 1) + a.f) * c.np * 4, gr0, gr1, &pr.s);
+    else if constexpr (GEN == 3) plb_grid_cell_adj_gen<false, true>(c, pr.p, lin, cell[0], cell + 1, g, a.w.pos + ((long)b * (c.S + 1) + a.f) * c.np * 3, a.softness + b * c.np, gout, q0, qs,
+                                                                    gfric, nullptr, nullptr, nullptr, &pr.s);
+    else
     if constexpr (ROT) plb_grid_cell_adj_gen<true>(c, pr.p, lin, cell[0], cell + 1, g, a.w.pos + ((long)b * (c.S + 1) + a.f) * c.np * 3, a.softness + b * c.np, gout, q0, qs, gfric,
                                                    pr.r.rot + ((long)b * (c.S + 1) + a.f) * c.np * 4, gr0, gr1);
     else if constexpr (GEN == 1) plb_grid_cell_adj_gen(c, pr.p, lin, cell[0], cell + 1, g, a.w.pos + ((long)b * (c.S + 1) + a.f) * c.np * 3, a.softness + b * c.np, gout, q0, qs, gfric);
@@ -550,6 +556,30 @@ template <int GEN>
 __device__ __forceinline__ double plb_loss_dist(const PlbConst& c, const PlbPrimArg<GEN>& pr, int pi, const double* xp, const double* pp, double* grad, double* den,
                                                 const double* q = nullptr, double* gq = nullptr) {
   const double d[3] = {xp[0] - pp[0], xp[1] - pp[1], xp[2] - pp[2]};
+  if constexpr (GEN == 3 || GEN == 4) {      // a shape handle: the kind's own sdf through the shape layer, its gradient the layer's adjoint of the distance alone
+    if (pr.p.kind[pi] != 0) {
+      constexpr bool ROT = GEN == 4;
+      [[maybe_unused]] double qi[4];
+      double pl[3];
+      if constexpr (ROT) plb_qinv(q, qi);
+      const double dist = plb_shape_local<ROT>(pr.p, pr.s, pi, c.radius[pi], d, pl, qi);
+      if (grad) {
+        const double zero[3] = {0, 0, 0};
+        [[maybe_unused]] double g[3];
+        plb_shape_local_adj<ROT>(pr.p, pr.s, pi, pl, 1.0, zero, zero, grad, qi, g);
+        *den = 1.0;
+        if constexpr (ROT) {
+          if (gq) {
+            double gqi[4];
+            plb_qrot_adj_rot(qi, d, g, gqi);
+            gq[0] = 0.0; gq[1] = 0.0; gq[2] = 0.0; gq[3] = 0.0;
+            plb_qinv_adj(q, qi, gqi, gq);
+          }
+        }
+      }
+      return dist;
+    }
+  } else
   if constexpr (GEN == 2) {
     if (pr.p.kind[pi] == 1) {
       double qi[4], pl[3], p[3], pass_y;
@@ -587,7 +617,7 @@ __device__ __forceinline__ double plb_loss_dist(const PlbConst& c, const PlbPrim
   return len - c.radius[pi];
 }
 
-template <int GEN>   // 2: a rot_state handle, the primitive's current rotation per env in pr.r.rot [B][np][4]
+template <int GEN>   // 2: a rot_state handle, the primitive's current rotation per env in pr.r.rot [B][np][4]; 3 / 4: a shape handle without / with it
 __global__ void __launch_bounds__(256) plb_loss_contact(PlbConst c, PlbPrimArg<GEN> pr, const double* x, const double* prim_pos, int soft, double* lred) {
   __shared__ double sh[4];
   const int b = blockIdx.y, p = blockIdx.x * blockDim.x + threadIdx.x;
@@ -596,7 +626,7 @@ __global__ void __launch_bounds__(256) plb_loss_contact(PlbConst c, PlbPrimArg<G
     if (p < c.N) {
       const double* xp = x + ((long)b * c.N + p) * 3;
       const double* pp = prim_pos + ((long)b * c.np + pi) * 3;
-      if constexpr (GEN == 2) dij = fmax(plb_loss_dist<GEN>(c, pr, pi, xp, pp, nullptr, nullptr, pr.r.rot + ((long)b * c.np + pi) * 4), 0.0);
+      if constexpr (GEN == 2 || GEN == 4) dij = fmax(plb_loss_dist<GEN>(c, pr, pi, xp, pp, nullptr, nullptr, pr.r.rot + ((long)b * c.np + pi) * 4), 0.0);
       else dij = fmax(plb_loss_dist<GEN>(c, pr, pi, xp, pp, nullptr, nullptr), 0.0);
       sw = 1.0 / (1.0 + dij * dij * 10000.0);
     }
@@ -633,7 +663,7 @@ template <int GEN>   // 2: prim_rot in pr.r.rot, g_prim_rot in pr.r.grot (may be
 __global__ void __launch_bounds__(256) plb_loss_bwd_kernel(PlbConst c, PlbPrimArg<GEN> pr, long G, int soft, const double* wts, const double* x, const double* prim_pos,
                                                           const double* td, const double* tsdf, const double* gm, const double* lred,
                                                           const double* g_loss, double* g_x, double* g_pp) {
-  constexpr bool ROT = GEN == 2;
+  constexpr bool ROT = GEN == 2 || GEN == 4;
   [[maybe_unused]] const double* prim_rot = nullptr;
   [[maybe_unused]] double* g_pr = nullptr;
   if constexpr (ROT) { prim_rot = pr.r.rot; g_pr = pr.r.grot; }
@@ -691,7 +721,7 @@ __global__ void __launch_bounds__(256) plb_loss_bwd_kernel(PlbConst c, PlbPrimAr
       }
     }
     if constexpr (ROT) {      // wave sum behind a wave-uniform test, one atomic per wave and word (as plb_grid_adj)
-      if (g_pr && pr.p.kind[pi] == 1 && __any(gqs[0] != 0.0 || gqs[1] != 0.0 || gqs[2] != 0.0 || gqs[3] != 0.0)) {
+      if (g_pr && plb_general<GEN == 4>(pr.p.kind[pi]) && __any(gqs[0] != 0.0 || gqs[1] != 0.0 || gqs[2] != 0.0 || gqs[3] != 0.0)) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           const double sm = plb_wave_sum(gqs[k]);
@@ -745,13 +775,17 @@ static int plb_step_bwd_impl(const char* who, bool rot, ud_plb* h, int B, const 
   for (int f = S - 1; f >= 0; --f) {
     a.f = f; a.epoch = h->epoch++; a.hs_in = f; a.hs_out = f + 1; a.lb = f & 1; a.ls = a.lb; a.lprev = a.lb ^ 1; a.lnext = a.lprev;
     if (!never_recompute) ud::plb_launch_p2g(a, lanes, lanes > 1 ? gq : gp, st);   // recompute (m, mv) (rewrites F[f + 1] with the same values); envs with a checkpointed substep leave at once
-    if (rot) hipLaunchKernelGGL(ud::plb_grid_keep<2>, gc, blk, 0, st, a, ud::PlbPrimArg<2>{h->prim, rr});
+    if (rot && h->shape) hipLaunchKernelGGL(ud::plb_grid_keep<4>, gc, blk, 0, st, a, ud::PlbPrimArg<4>{h->prim, rr, h->shp});
+    else if (h->shape) hipLaunchKernelGGL(ud::plb_grid_keep<3>, gc, blk, 0, st, a, ud::PlbPrimArg<3>{h->prim, h->shp});
+    else if (rot) hipLaunchKernelGGL(ud::plb_grid_keep<2>, gc, blk, 0, st, a, ud::PlbPrimArg<2>{h->prim, rr});
     else if (h->gen) hipLaunchKernelGGL(ud::plb_grid_keep<1>, gc, blk, 0, st, a, ud::PlbPrimArg<1>{h->prim});
     else hipLaunchKernelGGL(ud::plb_grid_keep<0>, gc, blk, 0, st, a, ud::PlbPrimArg<0>{});
     if (lanes == 8) hipLaunchKernelGGL(ud::plb_g2p_adj<8>, gq, blk, 0, st, a, (f + 1) & 1);
     else if (lanes == 4) hipLaunchKernelGGL(ud::plb_g2p_adj<4>, gq, blk, 0, st, a, (f + 1) & 1);
     else hipLaunchKernelGGL(ud::plb_g2p_adj<1>, gp, blk, 0, st, a, (f + 1) & 1);
-    if (rot) hipLaunchKernelGGL(ud::plb_grid_adj<2>, gc, blk, 0, st, a, ud::PlbPrimArg<2>{h->prim, rr});
+    if (rot && h->shape) hipLaunchKernelGGL(ud::plb_grid_adj<4>, gc, blk, 0, st, a, ud::PlbPrimArg<4>{h->prim, rr, h->shp});
+    else if (h->shape) hipLaunchKernelGGL(ud::plb_grid_adj<3>, gc, blk, 0, st, a, ud::PlbPrimArg<3>{h->prim, h->shp});
+    else if (rot) hipLaunchKernelGGL(ud::plb_grid_adj<2>, gc, blk, 0, st, a, ud::PlbPrimArg<2>{h->prim, rr});
     else if (h->gen) hipLaunchKernelGGL(ud::plb_grid_adj<1>, gc, blk, 0, st, a, ud::PlbPrimArg<1>{h->prim});
     else hipLaunchKernelGGL(ud::plb_grid_adj<0>, gc, blk, 0, st, a, ud::PlbPrimArg<0>{});
     if (lanes == 8) hipLaunchKernelGGL(ud::plb_p2g_adj<8>, gqa, dim3(128), 0, st, a, (f + 1) & 1);
@@ -812,7 +846,9 @@ static int plb_loss_common(ud_plb* h, int B, const double* x, const double* prim
   if (c.np > 0) {
     ud::PlbRot rr = h->rot;
     rr.rot = const_cast<double*>(prim_rot); rr.grot = nullptr;
-    if (prim_rot) hipLaunchKernelGGL(ud::plb_loss_contact<2>, gp, blk, 0, st, c, ud::PlbPrimArg<2>{h->prim, rr}, x, prim_pos, soft_contact, h->lred);
+    if (prim_rot && h->shape) hipLaunchKernelGGL(ud::plb_loss_contact<4>, gp, blk, 0, st, c, ud::PlbPrimArg<4>{h->prim, rr, h->shp}, x, prim_pos, soft_contact, h->lred);
+    else if (h->shape) hipLaunchKernelGGL(ud::plb_loss_contact<3>, gp, blk, 0, st, c, ud::PlbPrimArg<3>{h->prim, h->shp}, x, prim_pos, soft_contact, h->lred);
+    else if (prim_rot) hipLaunchKernelGGL(ud::plb_loss_contact<2>, gp, blk, 0, st, c, ud::PlbPrimArg<2>{h->prim, rr}, x, prim_pos, soft_contact, h->lred);
     else if (h->gen) hipLaunchKernelGGL(ud::plb_loss_contact<1>, gp, blk, 0, st, c, ud::PlbPrimArg<1>{h->prim}, x, prim_pos, soft_contact, h->lred);
     else hipLaunchKernelGGL(ud::plb_loss_contact<0>, gp, blk, 0, st, c, ud::PlbPrimArg<0>{}, x, prim_pos, soft_contact, h->lred);
   }
@@ -841,7 +877,11 @@ static int plb_loss_bwd_impl(const char* who, ud_plb* h, int B, const double* x,
   const dim3 blk(256), gp((h->c.N + 255) / 256, B);
   ud::PlbRot rr = h->rot;
   rr.rot = const_cast<double*>(prim_rot); rr.grot = g_prim_rot;
-  if (prim_rot) hipLaunchKernelGGL(ud::plb_loss_bwd_kernel<2>, gp, blk, 0, st, h->c, ud::PlbPrimArg<2>{h->prim, rr}, h->G, soft_contact, weights, x, prim_pos,
+  if (prim_rot && h->shape) hipLaunchKernelGGL(ud::plb_loss_bwd_kernel<4>, gp, blk, 0, st, h->c, ud::PlbPrimArg<4>{h->prim, rr, h->shp}, h->G, soft_contact, weights, x, prim_pos,
+                                               target_density, target_sdf, (const double*)h->gm, (const double*)h->lred, g_loss, g_x, g_prim_pos);
+  else if (h->shape) hipLaunchKernelGGL(ud::plb_loss_bwd_kernel<3>, gp, blk, 0, st, h->c, ud::PlbPrimArg<3>{h->prim, h->shp}, h->G, soft_contact, weights, x, prim_pos,
+                                        target_density, target_sdf, (const double*)h->gm, (const double*)h->lred, g_loss, g_x, g_prim_pos);
+  else if (prim_rot) hipLaunchKernelGGL(ud::plb_loss_bwd_kernel<2>, gp, blk, 0, st, h->c, ud::PlbPrimArg<2>{h->prim, rr}, h->G, soft_contact, weights, x, prim_pos,
                                    target_density, target_sdf, (const double*)h->gm, (const double*)h->lred, g_loss, g_x, g_prim_pos);
   else if (h->gen) hipLaunchKernelGGL(ud::plb_loss_bwd_kernel<1>, gp, blk, 0, st, h->c, ud::PlbPrimArg<1>{h->prim}, h->G, soft_contact, weights, x, prim_pos,
                                  target_density, target_sdf, (const double*)h->gm, (const double*)h->lred, g_loss, g_x, g_prim_pos);

@@ -165,9 +165,10 @@ struct PlbScale { double s[3]; };   // action scale of primitive 0 (set_velocity
 // of its own, and plb_grid_cell left to the letter: the persistent kernels inline that one at the edge of their register budget, and a
 // Sphere-only handle runs exactly the code it always ran.
 // ROT (a rot_state handle): Q0 = the quaternions of the env's primitives at substep f, Q0 + np*4 at f + 1.
-template <bool ROT = false>
+// SH (a shape handle): every kind but 0 collides so, through the shape layer; sh = the handle's shape constants.
+template <bool ROT = false, bool SH = false>
 __device__ __forceinline__ void plb_grid_cell_gen(const PlbConst& c, const PlbPrim& pr, long lin, double m, const double* mv, const double* P0, const double* soft,
-                                                  double* vv, const double* Q0 = nullptr) {
+                                                  double* vv, const double* Q0 = nullptr, const PlbShape* sh = nullptr) {
   vv[0] = 0.0; vv[1] = 0.0; vv[2] = 0.0;
   if (!(m > 1e-12)) return;
   const int n = c.n_grid;
@@ -177,9 +178,9 @@ __device__ __forceinline__ void plb_grid_cell_gen(const PlbConst& c, const PlbPr
   const double gp[3] = {I[0] * c.dx, I[1] * c.dx, I[2] * c.dx};
   const double* P1 = P0 + c.np * 3;
   for (int pi = 0; pi < c.np; ++pi) {
-    if (pr.kind[pi] == 1) {
-      if constexpr (ROT) plb_collide_rot(pr, pi, c.radius[pi], c.dt, gp, P0 + pi * 3, P1 + pi * 3, Q0 + pi * 4, Q0 + (c.np + pi) * 4, soft[pi], vv);
-      else plb_collide(pr, pi, c.radius[pi], c.dt, gp, P0 + pi * 3, P1 + pi * 3, soft[pi], vv);
+    if (plb_general<SH>(pr.kind[pi])) {
+      if constexpr (ROT) plb_collide_rot<SH>(pr, pi, c.radius[pi], c.dt, gp, P0 + pi * 3, P1 + pi * 3, Q0 + pi * 4, Q0 + (c.np + pi) * 4, soft[pi], vv, sh);
+      else plb_collide<SH>(pr, pi, c.radius[pi], c.dt, gp, P0 + pi * 3, P1 + pi * 3, soft[pi], vv, sh);
       continue;
     }
     const double d0 = gp[0] - P0[pi * 3], d1 = gp[1] - P0[pi * 3 + 1], d2 = gp[2] - P0[pi * 3 + 2];
@@ -206,10 +207,13 @@ __device__ __forceinline__ void plb_grid_cell_gen(const PlbConst& c, const PlbPr
     if (I[d] > n - 3 && vv[d] > 0) vv[d] = 0;
   }
 }
-template <int GEN>   // 0: sticky Spheres only, 1: a general primitive, 2: a rot_state handle (Q0: the substep's quaternions, see plb_grid_cell_gen)
+template <int GEN>   // 0: sticky Spheres only, 1: a general primitive, 2: a rot_state handle (Q0: the substep's quaternions, see plb_grid_cell_gen);
+                     // 3 / 4: a shape handle (Box, Cylinder, Torus) with constant orientation / on rot_state
 __device__ __forceinline__ void plb_grid_cell_any(const PlbConst& c, const PlbPrimArg<GEN>& pr, long lin, double m, const double* mv, const double* P0,
                                                   const double* soft, double* vv, const double* Q0 = nullptr) {
-  if constexpr (GEN == 2) plb_grid_cell_gen<true>(c, pr.p, lin, m, mv, P0, soft, vv, Q0);
+  if constexpr (GEN == 4) plb_grid_cell_gen<true, true>(c, pr.p, lin, m, mv, P0, soft, vv, Q0, &pr.s);
+  else if constexpr (GEN == 3) plb_grid_cell_gen<false, true>(c, pr.p, lin, m, mv, P0, soft, vv, nullptr, &pr.s);
+  else if constexpr (GEN == 2) plb_grid_cell_gen<true>(c, pr.p, lin, m, mv, P0, soft, vv, Q0);
   else if constexpr (GEN == 1) plb_grid_cell_gen(c, pr.p, lin, m, mv, P0, soft, vv);
   else plb_grid_cell(c, lin, m, mv, P0, soft, vv);
 }
@@ -243,6 +247,8 @@ struct ud_plb {
   int sort_every = 8;       // forward calls between two sorts (<= 0: never sort)
   bool gen = false;         // some primitive is not a sticky Sphere: the GEN = true kernels of the multi-kernel path (plb_prim.h)
   ud::PlbPrim prim{};
+  bool shape = false;       // some primitive is a Box, a Cylinder or a Torus: the GEN = 3 / 4 kernels, which read the kind at run time
+  ud::PlbShape shp{};
   ud::PlbScale ascale{{1.0, 1.0, 1.0}};
   bool rot_state = false;   // every primitive's orientation is per-env state (the _rot entry points); rot: its arenas and kinematics
   ud::PlbRot rot{};

@@ -306,10 +306,11 @@ __device__ __forceinline__ void plb_grid_cell_adj(const PlbConst& c, long lin, d
 // ---- the same for a handle with a general primitive (plb_prim.h; a function of its own for the reason given at plb_grid_cell_gen).  A cell sends
 // two independent vectors per primitive: q1[pi] adds to gpos[f + 1][pi], q0[pi] adds to gpos[f][pi] (a sticky sphere sends q0 = -q1).
 // ROT (a rot_state handle): Q0 as in plb_grid_cell_gen; gr0[pi] / gr1[pi] = what the cell sends to the cotangents of rotation[f] / rotation[f + 1].
-template <bool ROT = false>
+// SH (a shape handle): as in plb_grid_cell_gen.
+template <bool ROT = false, bool SH = false>
 __device__ __forceinline__ void plb_grid_cell_adj_gen(const PlbConst& c, const PlbPrim& pr, long lin, double m, const double* mv, const double* gin, const double* P0,
                                                       const double* soft, double* ga, double q0[2][3], double q1[2][3], double& gfric,
-                                                      const double* Q0 = nullptr, double (*gr0)[4] = nullptr, double (*gr1)[4] = nullptr) {
+                                                      const double* Q0 = nullptr, double (*gr0)[4] = nullptr, double (*gr1)[4] = nullptr, const PlbShape* sh = nullptr) {
   ga[0] = 0; ga[1] = 0; ga[2] = 0; ga[3] = 0;
   if (!(m > 1e-12)) return;
   double g[3] = {gin[0], gin[1], gin[2]};
@@ -326,9 +327,9 @@ __device__ __forceinline__ void plb_grid_cell_adj_gen(const PlbConst& c, const P
   for (int pi = 0; pi < c.np; ++pi) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) uin[pi][k] = vv[k];
-    if (pr.kind[pi] == 1) {
-      if constexpr (ROT) stick[pi] = plb_collide_rot(pr, pi, c.radius[pi], c.dt, gp, P0 + pi * 3, P1 + pi * 3, Q0 + pi * 4, Q0 + (c.np + pi) * 4, soft[pi], vv);
-      else stick[pi] = plb_collide(pr, pi, c.radius[pi], c.dt, gp, P0 + pi * 3, P1 + pi * 3, soft[pi], vv);
+    if (plb_general<SH>(pr.kind[pi])) {
+      if constexpr (ROT) stick[pi] = plb_collide_rot<SH>(pr, pi, c.radius[pi], c.dt, gp, P0 + pi * 3, P1 + pi * 3, Q0 + pi * 4, Q0 + (c.np + pi) * 4, soft[pi], vv, sh);
+      else stick[pi] = plb_collide<SH>(pr, pi, c.radius[pi], c.dt, gp, P0 + pi * 3, P1 + pi * 3, soft[pi], vv, sh);
       continue;
     }
     const double d0 = gp[0] - P0[pi * 3], d1 = gp[1] - P0[pi * 3 + 1], d2 = gp[2] - P0[pi * 3 + 2];
@@ -389,15 +390,15 @@ __device__ __forceinline__ void plb_grid_cell_adj_gen(const PlbConst& c, const P
 #pragma unroll
   for (int pi = 1; pi >= 0; --pi) {
     if (!(pi < c.np && stick[pi])) continue;
-    if (pr.kind[pi] == 1) {      // the forward of this primitive again from the velocity that entered it, then in reverse
+    if (plb_general<SH>(pr.kind[pi])) {      // the forward of this primitive again from the velocity that entered it, then in reverse
       PlbCollide k;
       double gu[3];
       if constexpr (ROT) {
-        plb_collide_eval_rot(pr, pi, c.radius[pi], c.dt, gp, P0 + pi * 3, P1 + pi * 3, Q0 + pi * 4, Q0 + (c.np + pi) * 4, soft[pi], uin[pi], k);
-        plb_collide_adj_rot(pr, pi, c.dt, k, soft[pi], gp, P0 + pi * 3, Q0 + pi * 4, Q0 + (c.np + pi) * 4, g, gu, q0[pi], q1[pi], gr0[pi], gr1[pi]);
+        plb_collide_eval_rot<SH>(pr, pi, c.radius[pi], c.dt, gp, P0 + pi * 3, P1 + pi * 3, Q0 + pi * 4, Q0 + (c.np + pi) * 4, soft[pi], uin[pi], k, sh);
+        plb_collide_adj_rot<SH>(pr, pi, c.dt, k, soft[pi], gp, P0 + pi * 3, Q0 + pi * 4, Q0 + (c.np + pi) * 4, g, gu, q0[pi], q1[pi], gr0[pi], gr1[pi], sh);
       } else {
-        plb_collide_eval(pr, pi, c.radius[pi], c.dt, gp, P0 + pi * 3, P1 + pi * 3, soft[pi], uin[pi], k);
-        plb_collide_adj(pr, pi, c.dt, k, soft[pi], g, gu, q0[pi], q1[pi]);
+        plb_collide_eval<false, SH>(pr, pi, c.radius[pi], c.dt, gp, P0 + pi * 3, P1 + pi * 3, soft[pi], uin[pi], k, nullptr, nullptr, nullptr, sh);
+        plb_collide_adj<false, SH>(pr, pi, c.dt, k, soft[pi], g, gu, q0[pi], q1[pi], nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, sh);
       }
       g[0] = gu[0]; g[1] = gu[1]; g[2] = gu[2];
     } else {

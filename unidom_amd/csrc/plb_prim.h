@@ -34,6 +34,17 @@ struct PlbRot {
 template <int GEN> struct PlbPrimArg {};
 template <> struct PlbPrimArg<1> { PlbPrim p; };
 template <> struct PlbPrimArg<2> { PlbPrim p; PlbRot r; };
+// Shape constants of a handle with a Box, a Cylinder or a Torus (PlbPrim.kind 3 / 4 / 5): Box size (three half extents), Cylinder (h, r, -),
+// Torus (tx, ty, -).  Such a handle runs instantiations of its own (GEN = 3: constant orientation, 4: rot_state), whose general code goes
+// through the shape layer below with the primitive's kind read at run time (a Capsule may sit beside a new shape); PlbPrim is laid out as
+// before, so the kernels of every other handle take the arguments they always took.
+struct PlbShape { double c[2][3]; };
+template <> struct PlbPrimArg<3> { PlbPrim p; PlbShape s; };
+template <> struct PlbPrimArg<4> { PlbPrim p; PlbRot r; PlbShape s; };
+// which kinds take Primitive.collide: the Capsule alone in the instantiations of before, every kind but the sticky Sphere on a shape handle
+template <bool SH> __device__ __forceinline__ bool plb_general(int kind) {
+  if constexpr (SH) return kind != 0; else return kind == 1;
+}
 // the extra argument of the pack / unpack kernels: nothing, or the above
 template <bool ROT> struct PlbRotArg {};
 template <> struct PlbRotArg<true> { PlbRot r; };
@@ -160,28 +171,208 @@ __device__ __forceinline__ void plb_capsule_local_adj(const PlbPrim& pr, int pi,
   if constexpr (ROT) { gpl_all[0] = g[0]; gpl_all[1] = g[1]; gpl_all[2] = g[2]; }
 }
 
+// ---- shape layer: (kind, constants, pl = the point in the primitive's frame) -> signed distance and local normal, and the adjoint from their
+// cotangents to pl's.  Restated from primitives.py: Capsule :61-73, Cylinder :176-202, Torus :211-231, Box :241-269; length(x) = sqrt(x.x + 1e-14)
+// throughout (:8-14).  Constants of the adjoint: indicators, signs and the arm abs / min / max took.  The Box normal is the reference's central
+// difference of its own _sdf (d = 1e-4), and its adjoint the exact derivative of that formula: the analytic sdf gradient at the six samples.
+#define PLB_BOX_D 1e-4
+__device__ __forceinline__ double plb_sgn(double a) { return a > 0.0 ? 1.0 : (a < 0.0 ? -1.0 : 0.0); }
+// Box._sdf (:251-256) at y; grad (may be null): its gradient
+__device__ __forceinline__ double plb_box_sdf(const double* sz, const double* y, double* grad = nullptr) {
+  const double q[3] = {fabs(y[0]) - sz[0], fabs(y[1]) - sz[1], fabs(y[2]) - sz[2]};
+  const double m[3] = {fmax(q[0], 0.0), fmax(q[1], 0.0), fmax(q[2], 0.0)};
+  const double len = sqrt(m[0] * m[0] + m[1] * m[1] + m[2] * m[2] + 1e-14);
+  const double mx = fmax(q[0], fmax(q[1], q[2]));
+  if (grad) {
+    const int am = (q[0] >= q[1] && q[0] >= q[2]) ? 0 : (q[1] >= q[2] ? 1 : 2);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) grad[i] = plb_sgn(y[i]) * (m[i] / len + ((mx <= 0.0 && am == i) ? 1.0 : 0.0));
+  }
+  return len + fmin(mx, 0.0);
+}
+// the distance alone (all a cell outside the shell, and the contact loss, need)
+__device__ __forceinline__ double plb_shape_sdf(int kind, const double* sc, double ch, double radius, const double* pl) {
+  if (kind == 3) return plb_box_sdf(sc, pl);
+  if (kind == 4) {                                           // Cylinder: sc = (h, r), h the radial half extent and r the axial one
+    const double l = sqrt(pl[0] * pl[0] + pl[2] * pl[2] + 1e-14);
+    const double d0 = l - sc[0], d1 = fabs(pl[1]) - sc[1];
+    const double m0 = fmax(d0, 0.0), m1 = fmax(d1, 0.0);
+    return fmin(fmax(d0, d1), 0.0) + sqrt(m0 * m0 + m1 * m1 + 1e-14);
+  }
+  if (kind == 5) {                                           // Torus: sc = (tx, ty)
+    const double q0 = sqrt(pl[0] * pl[0] + pl[2] * pl[2] + 1e-14) - sc[0];
+    return sqrt(q0 * q0 + pl[1] * pl[1] + 1e-14) - sc[1];
+  }
+  const double py = pl[1] + ch / 2;                          // Capsule, as plb_capsule_local
+  const double p1 = py - fmin(fmax(py, 0.0), ch);
+  return sqrt(pl[0] * pl[0] + p1 * p1 + pl[2] * pl[2] + 1e-14) - radius;
+}
+// n / length(n) and its adjoint (gn assigned)
+__device__ __forceinline__ void plb_normalize3(const double* n, double* o) {
+  const double il = 1.0 / sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2] + 1e-14);
+  o[0] = n[0] * il; o[1] = n[1] * il; o[2] = n[2] * il;
+}
+__device__ __forceinline__ void plb_normalize3_adj(const double* n, const double* go, double* gn) {
+  const double il = 1.0 / sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2] + 1e-14);
+  const double s = (go[0] * n[0] + go[1] * n[1] + go[2] * n[2]) * il * il * il;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) gn[k] = go[k] * il - s * n[k];
+}
+// the local normal (_normal of the kind)
+__device__ __forceinline__ void plb_shape_normal(int kind, const double* sc, double ch, const double* pl, double* nl) {
+  if (kind == 3) {                                           // Box: central differences of _sdf, normalised (:259-269)
+    double n[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      double inc[3] = {pl[0], pl[1], pl[2]}, dec[3] = {pl[0], pl[1], pl[2]};
+      inc[i] += PLB_BOX_D; dec[i] -= PLB_BOX_D;
+      n[i] = (0.5 / PLB_BOX_D) * (plb_box_sdf(sc, inc) - plb_box_sdf(sc, dec));
+    }
+    plb_normalize3(n, nl);
+  } else if (kind == 4) {                                    // Cylinder (:189-202)
+    const double l = sqrt(pl[0] * pl[0] + pl[2] * pl[2] + 1e-14);
+    const double d0 = l - sc[0], d1 = fabs(pl[1]) - sc[1];
+    const double f = d0 > d1 ? 1.0 : 0.0, in = fmax(d0, d1) <= 0.0 ? 1.0 : 0.0;
+    const double n20 = fmax(d0, 0.0) + in * f, n21 = fmax(d1, 0.0) + in * (1 - f);
+    const double l2 = sqrt(n20 * n20 + n21 * n21 + 1e-14);
+    const double sy = pl[1] >= 0.0 ? 1.0 : -1.0;
+    const double n3[3] = {pl[0] / l * (n20 / l2), n21 / l2 * sy, pl[2] / l * (n20 / l2)};
+    plb_normalize3(n3, nl);
+  } else if (kind == 5) {                                    // Torus (:223-231)
+    const double l = sqrt(pl[0] * pl[0] + pl[2] * pl[2] + 1e-14);
+    const double q0 = l - sc[0], q1 = pl[1];
+    const double lq = sqrt(q0 * q0 + q1 * q1 + 1e-14);
+    const double n3[3] = {pl[0] / l * (q0 / lq), q1 / lq, pl[2] / l * (q0 / lq)};
+    plb_normalize3(n3, nl);
+  } else {                                                   // Capsule: p / len
+    const double py = pl[1] + ch / 2;
+    const double p1 = py - fmin(fmax(py, 0.0), ch);
+    const double il = 1.0 / sqrt(pl[0] * pl[0] + p1 * p1 + pl[2] * pl[2] + 1e-14);
+    nl[0] = pl[0] * il; nl[1] = p1 * il; nl[2] = pl[2] * il;
+  }
+}
+// cotangents (gdist of the distance, gnl of the local normal) -> cotangent of pl (assigned); the intermediates are formed again from pl
+__device__ __forceinline__ void plb_shape_adj(int kind, const double* sc, double ch, const double* pl, double gdist, const double* gnl, double* g) {
+  if (kind == 3) {
+    double n[3], dg[3][3], gn[3], gs[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {                            // n_i = (0.5 / d) (sdf(pl + d e_i) - sdf(pl - d e_i)): each sample once, value and gradient
+      double inc[3] = {pl[0], pl[1], pl[2]}, dec[3] = {pl[0], pl[1], pl[2]}, gi[3], gd[3];
+      inc[i] += PLB_BOX_D; dec[i] -= PLB_BOX_D;
+      n[i] = (0.5 / PLB_BOX_D) * (plb_box_sdf(sc, inc, gi) - plb_box_sdf(sc, dec, gd));
+#pragma unroll
+      for (int k = 0; k < 3; ++k) dg[i][k] = gi[k] - gd[k];
+    }
+    plb_normalize3_adj(n, gnl, gn);
+    plb_box_sdf(sc, pl, gs);
+    g[0] = gdist * gs[0]; g[1] = gdist * gs[1]; g[2] = gdist * gs[2];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const double w = gn[i] * (0.5 / PLB_BOX_D);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) g[k] += w * dg[i][k];
+    }
+  } else if (kind == 4) {
+    const double l = sqrt(pl[0] * pl[0] + pl[2] * pl[2] + 1e-14);
+    const double d0 = l - sc[0], d1 = fabs(pl[1]) - sc[1];
+    const double f = d0 > d1 ? 1.0 : 0.0, in = fmax(d0, d1) <= 0.0 ? 1.0 : 0.0;
+    const double m0 = fmax(d0, 0.0), m1 = fmax(d1, 0.0);
+    const double n20 = m0 + in * f, n21 = m1 + in * (1 - f);
+    const double l2 = sqrt(n20 * n20 + n21 * n21 + 1e-14);
+    const double sy = pl[1] >= 0.0 ? 1.0 : -1.0;
+    const double a0 = n20 / l2, a1 = n21 / l2, px = pl[0] / l, pz = pl[2] / l;
+    const double n3[3] = {px * a0, a1 * sy, pz * a0};
+    double gn3[3];
+    plb_normalize3_adj(n3, gnl, gn3);
+    const double gpx = gn3[0] * a0, gpz = gn3[2] * a0;
+    const double ga0 = gn3[0] * px + gn3[2] * pz, ga1 = gn3[1] * sy;
+    const double s2 = (ga0 * n20 + ga1 * n21) / (l2 * l2 * l2);        // a = n2 / length(n2)
+    const double gn20 = ga0 / l2 - s2 * n20, gn21 = ga1 / l2 - s2 * n21;
+    // the distance: min(max(d0, d1), 0) + length(max(d, 0))
+    const double ls = sqrt(m0 * m0 + m1 * m1 + 1e-14);
+    const double gd0 = (d0 > 0.0 ? gn20 : 0.0) + gdist * (m0 / ls + (in * f)), gd1 = (d1 > 0.0 ? gn21 : 0.0) + gdist * (m1 / ls + in * (1 - f));
+    const double gl = gd0 - (gpx * pl[0] + gpz * pl[2]) / (l * l);      // d0 = l - h, p / l
+    g[0] = gpx / l + gl * pl[0] / l; g[2] = gpz / l + gl * pl[2] / l;
+    g[1] = gd1 * plb_sgn(pl[1]);
+  } else if (kind == 5) {
+    const double l = sqrt(pl[0] * pl[0] + pl[2] * pl[2] + 1e-14);
+    const double q0 = l - sc[0], q1 = pl[1];
+    const double lq = sqrt(q0 * q0 + q1 * q1 + 1e-14);
+    const double a0 = q0 / lq, a1 = q1 / lq, px = pl[0] / l, pz = pl[2] / l;
+    const double n3[3] = {px * a0, a1, pz * a0};
+    double gn3[3];
+    plb_normalize3_adj(n3, gnl, gn3);
+    const double gpx = gn3[0] * a0, gpz = gn3[2] * a0;
+    const double ga0 = gn3[0] * px + gn3[2] * pz, ga1 = gn3[1];
+    const double s2 = (ga0 * q0 + ga1 * q1) / (lq * lq * lq);
+    const double gq0 = ga0 / lq - s2 * q0 + gdist * a0, gq1 = ga1 / lq - s2 * q1 + gdist * a1;
+    const double gl = gq0 - (gpx * pl[0] + gpz * pl[2]) / (l * l);
+    g[0] = gpx / l + gl * pl[0] / l; g[2] = gpz / l + gl * pl[2] / l;
+    g[1] = gq1;
+  } else {                                                   // Capsule, as plb_capsule_local_adj
+    const double py = pl[1] + ch / 2;
+    const double p[3] = {pl[0], py - fmin(fmax(py, 0.0), ch), pl[2]};
+    const double pass_y = (py >= 0.0 && py <= ch) ? 0.0 : 1.0;
+    const double il = 1.0 / sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2] + 1e-14);
+    const double gl = gdist - (gnl[0] * p[0] + gnl[1] * p[1] + gnl[2] * p[2]) * il * il;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) g[k] = gnl[k] * il + gl * p[k] * il;
+    g[1] *= pass_y;
+  }
+}
+// the pair the contact goes through on a shape handle, behind inv_trans as plb_capsule_local / _adj are: d = point - position -> pl and the distance
+template <bool ROT = false>
+__device__ __forceinline__ double plb_shape_local(const PlbPrim& pr, const PlbShape& sh, int pi, double radius, const double* d, double* pl, const double* qi = nullptr) {
+  plb_qrot(plb_sel<ROT>(pr.qi[pi], qi), d, pl);
+  return plb_shape_sdf(pr.kind[pi], sh.c[pi], pr.h[pi], radius, pl);
+}
+// cotangents (gdist, gnl, gpl of pl directly) -> cotangent of d; ROT: also gpl_all, the whole cotangent of pl
+template <bool ROT = false>
+__device__ __forceinline__ void plb_shape_local_adj(const PlbPrim& pr, const PlbShape& sh, int pi, const double* pl, double gdist, const double* gnl, const double* gpl,
+                                                    double* gd, const double* qi = nullptr, double* gpl_all = nullptr) {
+  double g[3];
+  plb_shape_adj(pr.kind[pi], sh.c[pi], pr.h[pi], pl, gdist, gnl, g);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) g[k] += gpl[k];
+  plb_qrot_t(plb_sel<ROT>(pr.qi[pi], qi), g, gd);
+  if constexpr (ROT) { gpl_all[0] = g[0]; gpl_all[1] = g[1]; gpl_all[2] = g[2]; }
+}
+
+
 // everything Primitive.collide (primive_base.py:91-115) computes for one cell, kept for the adjoint
 struct PlbCollide {
   bool active, flag;
   double pl[3], p[3], pass_y, len, dist, D[3], e, infl, cv[3], w[3], nc, mn, t[3], tn, arg, ts[3];
 };
+// what p holds differs by handle: the Capsule's unnormalised vector from the axis segment (with len and pass_y beside it), and on a shape handle
+// (SH) the unit local normal itself, len and pass_y unused.  Read the unit local normal through this, never through p directly.
+template <bool SH> __device__ __forceinline__ void plb_local_normal(const PlbCollide& k, double* nl) {
+  if constexpr (SH) { nl[0] = k.p[0]; nl[1] = k.p[1]; nl[2] = k.p[2]; }
+  else { nl[0] = k.p[0] / k.len; nl[1] = k.p[1] / k.len; nl[2] = k.p[2] / k.len; }
+}
 // gp: cell position, P0 / P1: the primitive's position at substeps f / f + 1, sf: softness, u: the cell velocity so far; ROT: q0 / qi / q1 =
 // rotation[f], conj / |.| of it, rotation[f + 1]
-template <bool ROT = false>
+// SH (a shape handle): distance and normal through the shape layer, sh = the handle's shape constants
+template <bool ROT = false, bool SH = false>
 __device__ __forceinline__ void plb_collide_eval(const PlbPrim& pr, int pi, double radius, double dt, const double* gp, const double* P0, const double* P1,
                                                  double sf, const double* u, PlbCollide& k, const double* q0 = nullptr, const double* qi = nullptr,
-                                                 const double* q1 = nullptr) {
+                                                 const double* q1 = nullptr, const PlbShape* sh = nullptr) {
   const double d[3] = {gp[0] - P0[0], gp[1] - P0[1], gp[2] - P0[2]};
-  k.len = plb_capsule_local<ROT>(pr, pi, d, k.pl, k.p, k.pass_y, qi);
-  k.dist = k.len - radius;
+  if constexpr (SH) {
+    k.dist = plb_shape_local<ROT>(pr, *sh, pi, radius, d, k.pl, qi);
+  } else {
+    k.len = plb_capsule_local<ROT>(pr, pi, d, k.pl, k.p, k.pass_y, qi);
+    k.dist = k.len - radius;
+  }
   k.e = exp(-k.dist * sf);
   k.infl = fmin(k.e, 1.0);
   k.active = (sf > 0 && k.infl > 0.1) || k.dist <= 0;       // no 0.001 and no trailing `and softness > 0`: those are the Sphere override's
   k.flag = false;
   if (!k.active) return;
-  const double nl[3] = {k.p[0] / k.len, k.p[1] / k.len, k.p[2] / k.len};
+  if constexpr (SH) plb_shape_normal(pr.kind[pi], sh->c[pi], pr.h[pi], k.pl, k.p);
+  double nl[3], back[3];
+  plb_local_normal<SH>(k, nl);
   plb_qrot(plb_sel<ROT>(pr.q[pi], q0), nl, k.D);
-  double back[3];
   plb_qrot(plb_sel<ROT>(pr.q[pi], q1), k.pl, back);          // constant orientation: rotation[f + 1] = rotation[f]
 #pragma unroll
   for (int i = 0; i < 3; ++i) { k.cv[i] = (back[i] + P1[i] - gp[i]) / dt; k.w[i] = u[i] - k.cv[i]; }
@@ -198,26 +389,29 @@ __device__ __forceinline__ void plb_collide_eval(const PlbPrim& pr, int pi, doub
   for (int i = 0; i < 3; ++i) k.ts[i] = k.flag ? k.t[i] / k.tn * s : k.t[i];
 }
 // u <- collide(u); returns whether the primitive acted on the cell
+template <bool SH = false>
 __device__ __forceinline__ bool plb_collide(const PlbPrim& pr, int pi, double radius, double dt, const double* gp, const double* P0, const double* P1, double sf,
-                                            double* u) {
+                                            double* u, const PlbShape* sh = nullptr) {
   PlbCollide k;
-  plb_collide_eval(pr, pi, radius, dt, gp, P0, P1, sf, u, k);
+  plb_collide_eval<false, SH>(pr, pi, radius, dt, gp, P0, P1, sf, u, k, nullptr, nullptr, nullptr, sh);
   if (!k.active) return false;
 #pragma unroll
   for (int i = 0; i < 3; ++i) u[i] = k.cv[i] + k.w[i] * (1 - k.infl) + k.ts[i] * k.infl;
   return true;
 }
 // the same on a rot_state handle: q0 / q1 = rotation[f] / rotation[f + 1] of this env and primitive
+template <bool SH = false>
 __device__ __forceinline__ void plb_collide_eval_rot(const PlbPrim& pr, int pi, double radius, double dt, const double* gp, const double* P0, const double* P1,
-                                                     const double* q0, const double* q1, double sf, const double* u, PlbCollide& k) {
+                                                     const double* q0, const double* q1, double sf, const double* u, PlbCollide& k, const PlbShape* sh = nullptr) {
   double qi[4];
   plb_qinv(q0, qi);
-  plb_collide_eval<true>(pr, pi, radius, dt, gp, P0, P1, sf, u, k, q0, qi, q1);
+  plb_collide_eval<true, SH>(pr, pi, radius, dt, gp, P0, P1, sf, u, k, q0, qi, q1, sh);
 }
+template <bool SH = false>
 __device__ __forceinline__ bool plb_collide_rot(const PlbPrim& pr, int pi, double radius, double dt, const double* gp, const double* P0, const double* P1,
-                                                const double* q0, const double* q1, double sf, double* u) {
+                                                const double* q0, const double* q1, double sf, double* u, const PlbShape* sh = nullptr) {
   PlbCollide k;
-  plb_collide_eval_rot(pr, pi, radius, dt, gp, P0, P1, q0, q1, sf, u, k);
+  plb_collide_eval_rot<SH>(pr, pi, radius, dt, gp, P0, P1, q0, q1, sf, u, k, sh);
   if (!k.active) return false;
 #pragma unroll
   for (int i = 0; i < 3; ++i) u[i] = k.cv[i] + k.w[i] * (1 - k.infl) + k.ts[i] * k.infl;
@@ -226,10 +420,10 @@ __device__ __forceinline__ bool plb_collide_rot(const PlbPrim& pr, int pi, doubl
 // adjoint of an ACTIVE collide: G = cotangent of u_out (in), cotangent of u_in (out, may alias nothing of the inputs); g0 / g1 = cotangents of P_f / P_{f+1}.
 // ROT: also gq0 / gq1 = cotangents of rotation[f] (through the normal's rotation back, the local point and the inverse with its normalisation) and of
 // rotation[f + 1] (through the collider velocity), assigned; d = cell - P_f.
-template <bool ROT = false>
+template <bool ROT = false, bool SH = false>
 __device__ __forceinline__ void plb_collide_adj(const PlbPrim& pr, int pi, double dt, const PlbCollide& k, double sf, const double* G, double* gu, double* g0,
                                                 double* g1, const double* q0 = nullptr, const double* qi = nullptr, const double* q1 = nullptr,
-                                                const double* d = nullptr, double* gq0 = nullptr, double* gq1 = nullptr) {
+                                                const double* d = nullptr, double* gq0 = nullptr, double* gq1 = nullptr, const PlbShape* sh = nullptr) {
   double gcv[3], gw[3], gt[3], gD[3];
   double ginfl = 0, gnc = 0;
 #pragma unroll
@@ -265,25 +459,27 @@ __device__ __forceinline__ void plb_collide_adj(const PlbPrim& pr, int pi, doubl
   plb_qrot_t(plb_sel<ROT>(pr.q[pi], q1), gback, gpl);
   plb_qrot_t(plb_sel<ROT>(pr.q[pi], q0), gD, gnl);
   [[maybe_unused]] double gpl_all[3];
-  plb_capsule_local_adj<ROT>(pr, pi, k.p, k.len, k.pass_y, glen, gnl, gpl, gd, qi, gpl_all);
+  if constexpr (SH) plb_shape_local_adj<ROT>(pr, *sh, pi, k.pl, glen, gnl, gpl, gd, qi, gpl_all);
+  else plb_capsule_local_adj<ROT>(pr, pi, k.p, k.len, k.pass_y, glen, gnl, gpl, gd, qi, gpl_all);
 #pragma unroll
   for (int i = 0; i < 3; ++i) g0[i] = -gd[i];                // d = g - P_f
   if constexpr (ROT) {
-    const double nl[3] = {k.p[0] / k.len, k.p[1] / k.len, k.p[2] / k.len};
-    double gqi[4];
+    double nl[3], gqi[4];
+    plb_local_normal<SH>(k, nl);
     plb_qrot_adj_rot(q1, k.pl, gback, gq1);
     plb_qrot_adj_rot(q0, nl, gD, gq0);
     plb_qrot_adj_rot(qi, d, gpl_all, gqi);
     plb_qinv_adj(q0, qi, gqi, gq0);
   }
 }
+template <bool SH = false>
 __device__ __forceinline__ void plb_collide_adj_rot(const PlbPrim& pr, int pi, double dt, const PlbCollide& k, double sf, const double* gp, const double* P0,
                                                     const double* q0, const double* q1, const double* G, double* gu, double* g0, double* g1, double* gq0,
-                                                    double* gq1) {
+                                                    double* gq1, const PlbShape* sh = nullptr) {
   double qi[4];
   plb_qinv(q0, qi);
   const double d[3] = {gp[0] - P0[0], gp[1] - P0[1], gp[2] - P0[2]};
-  plb_collide_adj<true>(pr, pi, dt, k, sf, G, gu, g0, g1, q0, qi, q1, d, gq0, gq1);
+  plb_collide_adj<true, SH>(pr, pi, dt, k, sf, G, gu, g0, g1, q0, qi, q1, d, gq0, gq1, sh);
 }
 
 }  // namespace ud

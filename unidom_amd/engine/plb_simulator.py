@@ -59,6 +59,10 @@ class PlbConf:
     prim_h = (0.0, 0.0)
     prim_rot = ((1.0, 0.0, 0.0, 0.0), (1.0, 0.0, 0.0, 0.0))
     prim_friction = (0.0, 0.0)
+    # prim_kind 3 = Box, 4 = Cylinder, 5 = Torus (the base class's contact, as the Capsule): prim_shape holds the Box's three half extents
+    # `size`, the Cylinder's (h, r, -) -- h the radial half extent, r the axial one -- or the Torus's (tx, ty, -); prim_radius and prim_h of
+    # such a primitive are ignored (prim_radius still sets the number of primitives).  Kinds 0 to 2 ignore prim_shape
+    prim_shape = ((0.0, 0.0, 0.0), (0.0, 0.0, 0.0))
     action_scale = (1.0, 1.0, 1.0)
     # rotating primitives (ud_plb_conf.rot_state): every primitive's orientation is per-env state (PlbState.prim_rot, reset to prim_rot) and
     # turns once per substep; action_dim 6 = (v, w) of the base class, w scaled by action_scale_w; prim_kind 2 = RollingPin (three
@@ -334,6 +338,7 @@ class PlbSimulator:
         self.rot_state = bool(getattr(cfg, "rot_state", False))
         self.action_dim = int(getattr(cfg, "action_dim", 3)) or 3
         rot = (C.c_double * 4 * 2)(*[(C.c_double * 4)(*q) for q in pad(cfg.prim_rot, (0.0, 0.0, 0.0, 0.0))])
+        shape = (C.c_double * 3 * 2)(*[(C.c_double * 3)(*(list(sc) + [0.0] * 3)[:3]) for sc in pad(getattr(cfg, "prim_shape", ()), (0.0, 0.0, 0.0))])
         cc = _lib.ud_plb_conf(
             n_particles=self.n_particles, n_grid=self.n_grid, substeps=self.substeps, dt=self.dt,
             gravity=(C.c_double * 3)(*cfg.gravity), ground_friction=float(cfg.ground_friction), n_primitives=self.n_primitive,
@@ -343,7 +348,7 @@ class PlbSimulator:
             prim_kind=(C.c_int * 2)(*pad(cfg.prim_kind, 0)), capsule_h=(C.c_double * 2)(*pad(cfg.prim_h, 0.0)), prim_rot=rot,
             prim_friction=(C.c_double * 2)(*pad(cfg.prim_friction, 0.0)), action_scale=(C.c_double * 3)(*handle_scale),
             rot_state=int(self.rot_state), action_dim=int(getattr(cfg, "action_dim", 3)),
-            action_scale_w=(C.c_double * 3)(*getattr(cfg, "action_scale_w", (1.0, 1.0, 1.0))))
+            action_scale_w=(C.c_double * 3)(*getattr(cfg, "action_scale_w", (1.0, 1.0, 1.0))), prim_shape=shape)
         self._h = C.c_void_p()
         self.profile = None    # {"fwd": [], "bwd": []}: HIP-event pairs around every step call, on its stream (bench.py)
         self.ground_friction_grad = None   # [B], accumulated by backward() (optimize_ground_friction.grad); reset it by hand
