@@ -343,6 +343,25 @@ int ud_mpm_step_bwd(ud_mpm* h, int B, const void* ckpt, const float* prim_size, 
  *   rot[f+1] in the collider velocity (primive_base.py:82-89); its adjoint also reaches rot[f] (through the inverse with its
  *   normalisation, the local point and the normal's rotation back) and rot[f+1].  The reference asserts |q| > 0.9 (inv_trans); on the
  *   device this is the CALLER'S duty: prim_rot is not checked.  Specification: tests/plb_rot_twin.py.
+ * 6 Chopsticks (primitives.py:102-173; the *_gap entry points): two Capsules of (capsule_h, radius) = (h, r) side by side, the one kind whose
+ * SHAPE is state.  Beside position and rotation it carries its opening `gap` (the reference's state_dim = 8), which closes once per substep:
+ *   a = clip(action, -1, 1), seven dimensions;  v = a[0:3] action_scale / substeps, w = a[3:6] action_scale_w / substeps, gap_vel = a[6]
+ *     action_scale_gap / substeps;
+ *   gap[f+1] = max(gap[f] - gap_vel, min_gap);  pos[f+1] = clamp(pos[f] + v, lower_bound, upper_bound);  rot[f+1] = qmul(rot[f], w2quat(w)):
+ *     a RIGHT multiplication (a turn about the body's own axes), where the base class multiplies on the left.
+ *   Geometry at substep f, for the local point pl = qrot(conj(q) / |q|, g - P_f): p = pl + (0, h/2, 0), delta = (gap[f] / 2, 0, 0), a =
+ *   capsule_sdf(p - delta), b = capsule_sdf(p + delta) with capsule_sdf the Capsule's above, which shifts y by h/2 AGAIN before it takes off
+ *   clamp(y, 0, h): each stick's axis segment spans local y in [-h, 0] at x = -+gap/2 -- the primitive's position is the TOP END of the sticks, not
+ *   their middle (this doubled h/2 offset is the reference's, kept to the letter).  sdf = min(a, b); the local normal is the Capsule's normal of
+ *   stick a where a <= b (a tie takes stick a for both) and of stick b otherwise.  World normal, contact model and collider velocity are the
+ *   base class's, unchanged: the sticks' closing motion is NOT part of the collider velocity.
+ *   Adjoint: the selected stick and the arms of clamp / max are held constant.  gap[f] is a leaf of the contact at substep f: it enters through
+ *   -+delta in the selected stick's local point, so its cotangent is -+1/2 of the x-component of that point's cotangent (distance and normal).
+ *   Through max(gap - gap_vel, min_gap) the cotangent passes to gap[f] and -gap_vel where gap[f] - gap_vel > min_gap and is zero where it is
+ *   smaller; at exact equality it is UNSPECIFIED.  The right-multiplied step has its own adjoint; w's cotangent on the |w| <= 1e-9 arm is 0 as
+ *   above.  h, r, min_gap and the scales are not leaves.  Only primitive 0 can be a Chopsticks, on rot_state with action_dim = 7; primitive 1 is
+ *   the unactuated sticky Sphere of every rot_state handle (its gap entry is carried along unchanged).  Multi-kernel path only.
+ *   Specification: tests/plb_chopsticks_twin.py (the reference ships no chopsticks.yml and no recording).
  * Parity for these entry points is UNPINNED: taichi is absent and the reference ships no recording of this path; the torch
  * restatements (oracle/twin/plb_twin_torch.py, tests/plb_prim_twin.py for the Capsule) are the specification the kernels are held to.
  * ------------------------------------------------------------------------------------------------ */
@@ -382,7 +401,9 @@ typedef struct {
   /* Everything below: zero = the handle of before these fields existed (sticky Spheres, action scale 1) */
   int prim_kind[2];      /* 0 sticky Sphere, 1 Capsule (radius[i], capsule_h[i], prim_rot[i], prim_friction[i]), 2 RollingPin (the Capsule's
                             geometry, its own kinematics; needs rot_state and three action dimensions), 3 Box, 4 Cylinder, 5 Torus
-                            (prim_shape[i], prim_rot[i], prim_friction[i]; radius[i] and capsule_h[i] are ignored); else UD_ERR_INVALID.
+                            (prim_shape[i], prim_rot[i], prim_friction[i]; radius[i] and capsule_h[i] are ignored), 6 Chopsticks (radius[i],
+                            capsule_h[i], prim_friction[i], min_gap[i]; prim_shape ignored; primitive 0 only, needs rot_state and
+                            action_dim = 7: UD_ERR_INVALID without); else UD_ERR_INVALID.
                             A handle with any kind but 0 runs the multi-kernel path (path = 0 picks it; path = 2: UD_ERR_UNSUPPORTED) */
   double capsule_h[2];   /* Capsule: length of the axis segment (along the primitive's y), >= 0; radius[i] > 0 */
   double prim_rot[2][4]; /* Capsule: constant orientation (w, x, y, z); all four zero = identity, else |q| > 0.9 as the reference asserts */
@@ -393,10 +414,12 @@ typedef struct {
                                 then unused by the kernels).  Primitive 0 must be kind 1 to 5, primitive 1 (unactuated, never moves) a sticky
                                 Sphere: anything else, and path = 2, UD_ERR_UNSUPPORTED */
   int action_dim;            /* 0 or 3: three action dimensions.  6: (v, w) of the base class (set_velocity, primive_base.py:185-193); needs
-                                rot_state (UD_ERR_INVALID without) */
+                                rot_state (UD_ERR_INVALID without).  7: the Chopsticks' (v, w, gap_vel); UD_ERR_INVALID with any other kind */
   double action_scale_w[3];  /* action.scale[3:6]: w = clip(action[3:6], -1, 1) * action_scale_w / substeps; all zero = (1, 1, 1) */
   double prim_shape[2][3];   /* kinds 3 to 5: Box size (three half extents), Cylinder (h, r, -), Torus (tx, ty, -); a used constant <= 0 is
                                 UD_ERR_INVALID.  Kinds 0 to 2 ignore it (zero = the handle of before) */
+  double min_gap[2];         /* kind 6: Chopsticks.minimal_gap, >= 0 (the reference's default: 0.06); other kinds ignore it */
+  double action_scale_gap;   /* kind 6: action.scale[6], gap_vel = clip(action[6], -1, 1) * action_scale_gap / substeps; 0 = 1 */
 } ud_plb_conf;
 
 int ud_plb_create(const ud_plb_conf* conf, ud_plb** out);
@@ -428,6 +451,16 @@ int ud_plb_step_fwd_rot(ud_plb* h, int B, const double* x, const double* v, cons
                         const double* E, const double* nu, const double* yield_stress, double* x_out, double* v_out,
                         double* C_out, double* F_out, double* prim_pos_out, double* prim_rot_out, void* ckpt, void* stream);
 
+/* The same on a Chopsticks handle (prim_kind[0] = 6; UD_ERR_INVALID on any other, and ud_plb_step_fwd / _fwd_rot and their siblings return
+ * UD_ERR_INVALID on a Chopsticks handle, touch no output and name the reason): prim_gap [B,n_primitives] (primitive 1's entry is carried
+ * through), action [B,7], prim_gap_out [B,n_primitives].  The checkpoint also keeps the gap trajectory (ud_plb_ckpt_bytes grows for such
+ * handles only).  Launches only: no allocation, no synchronisation; graph-capturable like its siblings. */
+int ud_plb_step_fwd_gap(ud_plb* h, int B, const double* x, const double* v, const double* C, const double* F,
+                        const double* prim_pos, const double* prim_rot, const double* prim_gap, const double* softness,
+                        const double* action, const double* E, const double* nu, const double* yield_stress, double* x_out,
+                        double* v_out, double* C_out, double* F_out, double* prim_pos_out, double* prim_rot_out,
+                        double* prim_gap_out, void* ckpt, void* stream);
+
 /* Adjoint of one env.step.  g_x, g_v [B,N,3], g_C, g_F [B,N,3,3], g_prim_pos [B,n_primitives,3]: cotangents of the
  * step's outputs (any may be NULL = zero).  Outputs: cotangents of the inputs x, v, C, F (required), of prim_pos
  * [B,n_primitives,3], of action [B,3], and per env of E, nu, yield_stress and the ground friction [B] (each may be NULL).
@@ -444,6 +477,13 @@ int ud_plb_step_bwd_rot(ud_plb* h, int B, const void* ckpt, const double* softne
                         const double* g_F, const double* g_prim_pos, const double* g_prim_rot, double* g_x0, double* g_v0,
                         double* g_C0, double* g_F0, double* g_prim_pos0, double* g_prim_rot0, double* g_action, double* g_E,
                         double* g_nu, double* g_yield_stress, double* g_ground_friction, void* stream);
+/* ... of ud_plb_step_fwd_gap: also g_prim_gap [B,n_primitives] (in, may be NULL = zero), g_prim_gap0 [B,n_primitives] (out, may be NULL),
+ * g_action [B,7]. */
+int ud_plb_step_bwd_gap(ud_plb* h, int B, const void* ckpt, const double* softness, const double* action, const double* E,
+                        const double* nu, const double* yield_stress, const double* g_x, const double* g_v, const double* g_C,
+                        const double* g_F, const double* g_prim_pos, const double* g_prim_rot, const double* g_prim_gap, double* g_x0,
+                        double* g_v0, double* g_C0, double* g_F0, double* g_prim_pos0, double* g_prim_rot0, double* g_prim_gap0,
+                        double* g_action, double* g_E, double* g_nu, double* g_yield_stress, double* g_ground_friction, void* stream);
 
 /* Loss of a particle state (engine/losses/loss.py): x [B,N,3], prim_pos [B,n_primitives,3], target_density and target_sdf
  * [n_grid^3] (shared by the envs), weights [3] = (contact, density, sdf) -- all device arrays.
@@ -464,6 +504,14 @@ int ud_plb_loss_fwd_rot(ud_plb* h, int B, const double* x, const double* prim_po
 int ud_plb_loss_bwd_rot(ud_plb* h, int B, const double* x, const double* prim_pos, const double* prim_rot, const double* target_density,
                         const double* target_sdf, const double* weights, int soft_contact, const double* g_loss, double* g_x,
                         double* g_prim_pos, double* g_prim_rot, void* stream);
+/* The same on a Chopsticks handle: the contact term takes the Chopsticks' distance at the caller's current gap prim_gap [B,n_primitives];
+ * g_prim_gap [B,n_primitives] (out, may be NULL). */
+int ud_plb_loss_fwd_gap(ud_plb* h, int B, const double* x, const double* prim_pos, const double* prim_rot, const double* prim_gap,
+                        const double* target_density, const double* target_sdf, const double* weights, int soft_contact, double* loss,
+                        double* parts, void* stream);
+int ud_plb_loss_bwd_gap(ud_plb* h, int B, const double* x, const double* prim_pos, const double* prim_rot, const double* prim_gap,
+                        const double* target_density, const double* target_sdf, const double* weights, int soft_contact,
+                        const double* g_loss, double* g_x, double* g_prim_pos, double* g_prim_rot, double* g_prim_gap, void* stream);
 
 /* Grid mass of a particle state, the field a goal is made of (TaichiEnv.get_grid_mass; create_goal1.py saves it as the target
  * density): grid_mass [B, n_grid^3] = the loss's p2g of the particle masses, written into the caller's array (zeroed here, summed with

@@ -21,6 +21,7 @@ SYMBOLS = [
     "ud_mpm_create", "ud_mpm_destroy", "ud_mpm_ckpt_bytes", "ud_mpm_ckpt_cells", "ud_mpm_launch_plan", "ud_mpm_reset", "ud_mpm_step_fwd", "ud_mpm_step_bwd",
     "ud_plb_create", "ud_plb_destroy", "ud_plb_launch_plan", "ud_plb_poll_timeouts", "ud_plb_step_fwd", "ud_plb_ckpt_bytes", "ud_plb_step_bwd", "ud_plb_loss_fwd", "ud_plb_loss_bwd",
     "ud_plb_step_fwd_rot", "ud_plb_step_bwd_rot", "ud_plb_loss_fwd_rot", "ud_plb_loss_bwd_rot",
+    "ud_plb_step_fwd_gap", "ud_plb_step_bwd_gap", "ud_plb_loss_fwd_gap", "ud_plb_loss_bwd_gap",
     "ud_plb_grid_mass", "ud_plb_target_work_bytes", "ud_plb_target_sdf", "ud_plb_density_iou_work_bytes", "ud_plb_density_iou",
     "ud_plb_density_seq_work_bytes", "ud_plb_density_seq_sign_bytes", "ud_plb_density_seq_fwd", "ud_plb_density_seq_bwd", "ud_plb_chamfer",
     "ud_plb_policy_n_params", "ud_plb_policy_tape_bytes", "ud_plb_policy_fwd", "ud_plb_policy_bwd",
@@ -59,7 +60,7 @@ class ud_plb_conf(C.Structure):
                 ("prim_kind", C.c_int * 2), ("capsule_h", C.c_double * 2), ("prim_rot", (C.c_double * 4) * 2),
                 ("prim_friction", C.c_double * 2), ("action_scale", C.c_double * 3),
                 ("rot_state", C.c_int), ("action_dim", C.c_int), ("action_scale_w", C.c_double * 3),
-                ("prim_shape", (C.c_double * 3) * 2)]
+                ("prim_shape", (C.c_double * 3) * 2), ("min_gap", C.c_double * 2), ("action_scale_gap", C.c_double)]
 
 
 def build(force: bool = False) -> str:

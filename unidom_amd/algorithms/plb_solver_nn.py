@@ -25,6 +25,8 @@ class SolverNN:
     parameters are unbounded (solver_nn.py:6-7).  Returns the best parameters seen (:45-59), not the last ones as `Solver` does."""
 
     def __init__(self, sim, loss, policy, horizon=50, n_iters=100, softness=666.0, optim="Adam", lr=0.1, **optim_kwargs):
+        if getattr(sim, "chopsticks", False):       # the reference's MLP refuses a Chopsticks (engine/nn/mlp.py:26-27), and so does PlbPolicy
+            raise ValueError("SolverNN: a Chopsticks simulator (prim_kind[0] = 6) has no policy; optimise its actions with plb_solver.Solver")
         self.sim, self.loss, self.policy = sim, loss, policy
         self.horizon, self.n_iters, self.softness = int(horizon), int(n_iters), float(softness)
         self.optim_cls = OPTIMS[optim] if isinstance(optim, str) else optim

@@ -162,7 +162,8 @@ __global__ void __launch_bounds__(256) plb_p2g(PlbArgs a) {
 }
 
 // grid_op (:200-232) over the touched cells.  GEN: the handle has a general primitive (plb_prim.h), fixed at create
-template <int GEN>   // 2: a rot_state handle, the substep's two quaternions per primitive read from the rotation trajectory; 3 / 4: a shape handle without / with it
+template <int GEN>   // 2: a rot_state handle, the substep's two quaternions per primitive read from the rotation trajectory; 3 / 4: a shape handle without / with it;
+                     // 5: a Chopsticks handle, gap[f] read from the gap trajectory as well
 __global__ void __launch_bounds__(256) plb_grid(PlbArgs a, PlbPrimArg<GEN> pr) {
   const int b = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x;
   const PlbConst& c = a.c;
@@ -184,6 +185,9 @@ __global__ void __launch_bounds__(256) plb_grid(PlbArgs a, PlbPrimArg<GEN> pr) {
     o[0] = cell[0]; o[1] = cell[1]; o[2] = cell[2]; o[3] = cell[3];
   }
   double vv[3];
+  if constexpr (GEN == 5) plb_grid_cell_any<GEN>(c, pr, lin, cell[0], cell + 1, a.w.pos + ((long)b * (c.S + 1) + a.f) * c.np * 3, a.softness + b * c.np, vv,
+                                                 pr.r.rot + ((long)b * (c.S + 1) + a.f) * c.np * 4, pr.g.gap + ((long)b * (c.S + 1) + a.f) * c.np);
+  else
   if constexpr (GEN == 2 || GEN == 4) plb_grid_cell_any<GEN>(c, pr, lin, cell[0], cell + 1, a.w.pos + ((long)b * (c.S + 1) + a.f) * c.np * 3, a.softness + b * c.np, vv,
                                                  pr.r.rot + ((long)b * (c.S + 1) + a.f) * c.np * 4);
   else
@@ -421,6 +425,67 @@ __device__ __forceinline__ void plb_kinematics_rot(const PlbConst& c, const PlbR
   }
 }
 
+// The kinematics of a Chopsticks handle likewise (r.kin == 3): primitive 0 runs Chopsticks.forward_kinematics (primitives.py:113-128) -- seven action
+// dimensions, v, w, gap_vel = clip(action) * (scale, scale_w, scale_gap) / substeps; gap[f+1] = max(gap[f] - gap_vel, minimal_gap), pos[f+1] =
+// clamp(pos[f] + v), rot[f+1] = qmul(rot[f], w2quat(w)): the RIGHT multiplication -- primitive 1, the unactuated Sphere, the base class's with
+// v = w = 0 and a gap that stays what it was given.  Gp: the env's gap trajectory [S+1][np]; gap_out: the caller's prim_gap_out of the env.
+__device__ __forceinline__ void plb_kinematics_gap(const PlbConst& c, const PlbRot& r, const PlbGap& g, const PlbScale& sc, int b, int pi, const double* prim_pos,
+                                                   const double* prim_rot, const double* action, double* P, double* R, double* Gp, double* gap_out) {
+  double pos[3], q[4], av[7] = {0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+  for (int d = 0; d < 3; ++d) { pos[d] = prim_pos[((long)b * c.np + pi) * 3 + d]; P[pi * 3 + d] = pos[d]; }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) { q[k] = prim_rot[((long)b * c.np + pi) * 4 + k]; R[pi * 4 + k] = q[k]; }
+  double gap = g.ext[(long)b * c.np + pi];
+  Gp[pi] = gap;
+  if (pi == 0) {
+#pragma unroll
+    for (int d = 0; d < 7; ++d) av[d] = fmin(fmax(action[(long)b * 7 + d], -1.0), 1.0) * (d < 3 ? sc.s[d] : (d < 6 ? r.sw[d - 3] : g.sg)) / (double)c.S;
+  }
+  double dq[4];
+  plb_w2quat(av + 3, dq);
+  for (int s = 0; s < c.S; ++s) {
+    double q1[4];
+    if (pi == 0) { plb_qstep_right(q, dq, q1); gap = plb_gap_step(gap, av[6], g.mingap[pi]); }
+    else plb_qmul(dq, q, q1);
+#pragma unroll
+    for (int d = 0; d < 3; ++d) { pos[d] = fmax(fmin(pos[d] + av[d], c.hi[d]), c.lo[d]); P[((s + 1) * c.np + pi) * 3 + d] = pos[d]; }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { q[k] = q1[k]; R[((s + 1) * c.np + pi) * 4 + k] = q[k]; }
+    Gp[(s + 1) * c.np + pi] = gap;
+  }
+  gap_out[pi] = gap;
+}
+
+// one particle's state into slot 0 of the history, through the call's spatial order
+__device__ __forceinline__ void plb_pack_particle(const PlbArgs& a, int b, int p, const double* x, const double* v, const double* Cm, const double* F, const int* order) {
+  const PlbConst& c = a.c;
+  double* h = plb_hist(a, b, 0);
+  const int up = order ? order[(long)b * c.Np + p] : p;
+  a.w.perm[(long)b * c.Np + p] = up;
+  const long o3 = ((long)b * c.N + up) * 3, o9 = ((long)b * c.N + up) * 9;
+#pragma unroll
+  for (int d = 0; d < 3; ++d) { h[d * c.Np + p] = x[o3 + d]; h[(3 + d) * c.Np + p] = v[o3 + d]; }
+#pragma unroll
+  for (int d = 0; d < 9; ++d) { h[(6 + d) * c.Np + p] = Cm[o9 + d]; h[(15 + d) * c.Np + p] = F[o9 + d]; }
+}
+
+// plb_pack of a Chopsticks handle: the prologue runs plb_kinematics_gap (prim_rot = r.ext, prim_gap = g.ext) and, the whole trajectory being known
+// here, writes prim_gap_out (g.ext_out) at once; the end of the call is plb_unpack_clear<true>, as on every rot_state handle
+__global__ void __launch_bounds__(256) plb_pack_gap(PlbArgs a, const double* x, const double* v, const double* Cm, const double* F, const int* order,
+                                                    const double* prim_pos, const double* action, PlbScale sc, PlbRot r, PlbGap g) {
+  const int b = blockIdx.y, p = blockIdx.x * blockDim.x + threadIdx.x;
+  const PlbConst& c = a.c;
+  if (blockIdx.x == 0) {
+    if (threadIdx.x < c.np)
+      plb_kinematics_gap(c, r, g, sc, b, threadIdx.x, prim_pos, r.ext, action, a.w.pos + (long)b * (c.S + 1) * c.np * 3, r.rot + (long)b * (c.S + 1) * c.np * 4,
+                         g.gap + (long)b * (c.S + 1) * c.np, g.ext_out + (long)b * c.np);
+    if (threadIdx.x >= 64 && threadIdx.x < 67) a.w.count[(threadIdx.x - 64) * a.B + b] = 0;
+  }
+  if (p >= c.N) return;
+  plb_pack_particle(a, b, p, x, v, Cm, F, order);
+}
+
 template <bool ROT>   // a rot_state handle: one thread per primitive runs the serial kinematics above (prim_rot = rr.r.ext)
 __global__ void __launch_bounds__(256) plb_pack(PlbArgs a, const double* x, const double* v, const double* Cm, const double* F, const int* order,
                                                 const double* prim_pos, const double* action, PlbScale sc, PlbRotArg<ROT> rr) {
@@ -503,6 +568,7 @@ int plb_reserve(ud_plb* h, int B, bool multi_kernel) {
   // both paths: the spatial order, the loss kernels' grid mass and partial sums
   const size_t o_order = take((size_t)B * c.Np * 4), o_gm = take((size_t)B * h->G * 8), o_lred = take((size_t)B * 16 * 8);
   const size_t o_rot = h->rot_state ? take((size_t)B * (c.S + 1) * c.np * 4 * 8) : 0, o_grot = h->rot_state ? take((size_t)B * (c.S + 1) * c.np * 4 * 8) : 0;
+  const size_t o_gap = h->chop ? take((size_t)B * (c.S + 1) * c.np * 8) : 0, o_ggap = h->chop ? take((size_t)B * (c.S + 1) * c.np * 8) : 0;
   hipError_t e = hipMalloc(&h->arena, off);
   if (e != hipSuccess) { ud::set_error("ud_plb_create: hipMalloc(%zu MB) failed: %s", off >> 20, hipGetErrorString(e)); return UD_ERR_HIP; }
   e = hipMemset(h->arena, 0, off);
@@ -517,12 +583,13 @@ int plb_reserve(ud_plb* h, int B, bool multi_kernel) {
   }
   h->order = (int*)(base + o_order); h->gm = (double*)(base + o_gm); h->lred = (double*)(base + o_lred);
   if (h->rot_state) { h->rot.rot = (double*)(base + o_rot); h->rot.grot = (double*)(base + o_grot); }
+  if (h->chop) { h->gap.gap = (double*)(base + o_gap); h->gap.ggap = (double*)(base + o_ggap); }
   h->B = B; h->epoch = 1; h->sort_B = 0;
   return UD_OK;
 }
 
-// caller-owned checkpoint of one step call: hist[B][S+1][24][Np] | pos[B][S+1][np][3] | perm[B][Np] (int) | grid checkpoint | svd | rot[B][S+1][np][4]
-PlbCkOff plb_ckpt_layout(const ud::PlbConst& c, int B, bool rot) {
+// caller-owned checkpoint of one step call: hist[B][S+1][24][Np] | pos[B][S+1][np][3] | perm[B][Np] (int) | grid checkpoint | svd | rot[B][S+1][np][4] | gap[B][S+1][np]
+PlbCkOff plb_ckpt_layout(const ud::PlbConst& c, int B, bool rot, bool gap) {
   PlbCkOff k{};
   size_t off = 0;
   auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
@@ -534,6 +601,7 @@ PlbCkOff plb_ckpt_layout(const ud::PlbConst& c, int B, bool rot) {
   k.gck_val = take((size_t)B * c.S * c.gck * 32);
   k.svd = take((size_t)B * c.S * 21 * c.Np * 8);
   k.rot = rot ? take((size_t)B * (c.S + 1) * c.np * 4 * 8) : 0;   // rot_state handles: the rotation trajectory, behind everything else
+  k.gap = gap ? take((size_t)B * (c.S + 1) * c.np * 8) : 0;       // Chopsticks handles: the gap trajectory, behind that
   k.total = off;
   return k;
 }
@@ -572,11 +640,16 @@ int ud_plb_create(const ud_plb_conf* conf, ud_plb** out) {
   const bool unit_scale = h->ascale.s[0] == 1.0 && h->ascale.s[1] == 1.0 && h->ascale.s[2] == 1.0;
   // rotating primitives: orientation as per-env state, six action dimensions, the RollingPin's kinematics (all zero = none of it)
   h->rot_state = conf->rot_state != 0;
-  if (!(conf->action_dim == 0 || conf->action_dim == 3 || conf->action_dim == 6)) {
-    ud::set_error("ud_plb_create: action_dim = %d (0 or 3: three action dimensions, 6: (v, w))", conf->action_dim); delete h; return UD_ERR_INVALID;
+  if (!(conf->action_dim == 0 || conf->action_dim == 3 || conf->action_dim == 6 || conf->action_dim == 7)) {
+    ud::set_error("ud_plb_create: action_dim = %d (0 or 3: three action dimensions, 6: (v, w), 7: the Chopsticks' (v, w, gap_vel))", conf->action_dim); delete h; return UD_ERR_INVALID;
   }
-  if (conf->action_dim == 6 && !h->rot_state) { ud::set_error("ud_plb_create: action_dim = 6 requires rot_state"); delete h; return UD_ERR_INVALID; }
-  h->rot.adim = conf->action_dim == 6 ? 6 : 3;
+  if (conf->action_dim >= 6 && !h->rot_state && !(c.np > 0 && conf->prim_kind[0] == 6)) {   // (a Chopsticks names itself below)
+    ud::set_error("ud_plb_create: action_dim = %d requires rot_state", conf->action_dim); delete h; return UD_ERR_INVALID;
+  }
+  if (conf->action_dim == 7 && !(c.np > 0 && conf->prim_kind[0] == 6)) {
+    ud::set_error("ud_plb_create: action_dim = 7 is the Chopsticks' alone (prim_kind[0] = %d, not 6)", c.np > 0 ? conf->prim_kind[0] : 0); delete h; return UD_ERR_INVALID;
+  }
+  h->rot.adim = conf->action_dim >= 6 ? conf->action_dim : 3;
   h->rot.kin = 1;
   {
     const double* sw = conf->action_scale_w;
@@ -585,10 +658,22 @@ int ud_plb_create(const ud_plb_conf* conf, ud_plb** out) {
   }
   for (int pi = 0; pi < c.np; ++pi) {
     const int kind = conf->prim_kind[pi];
-    if (kind < 0 || kind > 5) { ud::set_error("ud_plb_create: prim_kind[%d] = %d (0 Sphere, 1 Capsule, 2 RollingPin, 3 Box, 4 Cylinder, 5 Torus)", pi, kind); delete h; return UD_ERR_INVALID; }
+    if (kind < 0 || kind > 6) { ud::set_error("ud_plb_create: prim_kind[%d] = %d (0 Sphere, 1 Capsule, 2 RollingPin, 3 Box, 4 Cylinder, 5 Torus, 6 Chopsticks)", pi, kind); delete h; return UD_ERR_INVALID; }
     if (kind == 2 && !h->rot_state) { ud::set_error("ud_plb_create: prim_kind[%d] = 2 (RollingPin) requires rot_state", pi); delete h; return UD_ERR_INVALID; }
+    if (kind == 6) {      // its gap and orientation are state, its kinematics take seven action dimensions
+      if (pi != 0) { ud::set_error("ud_plb_create: prim_kind[%d] = 6: a Chopsticks can only be primitive 0", pi); delete h; return UD_ERR_UNSUPPORTED; }
+      if (!h->rot_state || conf->action_dim != 7) {
+        ud::set_error("ud_plb_create: prim_kind[%d] = 6 (Chopsticks) needs rot_state and action_dim = 7 (rot_state = %d, action_dim = %d)", pi, conf->rot_state, conf->action_dim);
+        delete h; return UD_ERR_INVALID;
+      }
+      if (!(conf->min_gap[pi] >= 0)) { ud::set_error("ud_plb_create: min_gap[%d] = %g: a Chopsticks needs minimal_gap >= 0", pi, conf->min_gap[pi]); delete h; return UD_ERR_INVALID; }
+      h->chop = true;
+      h->rot.kin = 3;
+      h->gap.mingap[0] = conf->min_gap[0]; h->gap.mingap[1] = conf->min_gap[1];
+      h->gap.sg = conf->action_scale_gap == 0 ? 1.0 : conf->action_scale_gap;
+    }
     if (h->rot_state) {
-      if (pi == 0 && kind == 0) { ud::set_error("ud_plb_create: rot_state: primitive 0 must be a Capsule (1), a RollingPin (2), a Box (3), a Cylinder (4) or a Torus (5), not a sticky Sphere"); delete h; return UD_ERR_UNSUPPORTED; }
+      if (pi == 0 && kind == 0) { ud::set_error("ud_plb_create: rot_state: primitive 0 must be a Capsule (1), a RollingPin (2), a Box (3), a Cylinder (4), a Torus (5) or a Chopsticks (6), not a sticky Sphere"); delete h; return UD_ERR_UNSUPPORTED; }
       if (pi == 1 && kind != 0) { ud::set_error("ud_plb_create: rot_state: primitive 1 is unactuated and must be a sticky Sphere (prim_kind[1] = %d)", kind); delete h; return UD_ERR_UNSUPPORTED; }
       if (kind == 2 && h->rot.adim != 3) { ud::set_error("ud_plb_create: the RollingPin takes three action dimensions (dw, dth, dy), action_dim = %d", conf->action_dim); delete h; return UD_ERR_UNSUPPORTED; }
       if (kind == 2) h->rot.kin = 2;
@@ -602,7 +687,7 @@ int ud_plb_create(const ud_plb_conf* conf, ud_plb** out) {
       h->gen = true;
       if (!h->rot_state && !ident && !(std::sqrt(n2) > 0.9)) { ud::set_error("ud_plb_create: |prim_rot[%d]| = %g (the reference asserts > 0.9; all zero = identity)", pi, std::sqrt(n2)); delete h; return UD_ERR_INVALID; }
     }
-    if (kind >= 3) {      // Box: size; Cylinder: (h, r); Torus: (tx, ty) -- radius[pi] and capsule_h[pi] are ignored
+    if (kind >= 3 && kind <= 5) {      // Box: size; Cylinder: (h, r); Torus: (tx, ty) -- radius[pi] and capsule_h[pi] are ignored
       h->shape = true;
       const int used = kind == 3 ? 3 : 2;
       for (int k = 0; k < 3; ++k) {
@@ -616,7 +701,7 @@ int ud_plb_create(const ud_plb_conf* conf, ud_plb** out) {
       }
     } else if (kind != 0) {
       if (!(conf->capsule_h[pi] >= 0) || !(conf->radius[pi] > 0)) {
-        ud::set_error("ud_plb_create: Capsule %d needs capsule_h >= 0 and radius > 0 (h = %g, r = %g)", pi, conf->capsule_h[pi], conf->radius[pi]); delete h; return UD_ERR_INVALID;
+        ud::set_error("ud_plb_create: %s %d needs capsule_h >= 0 and radius > 0 (h = %g, r = %g)", kind == 6 ? "Chopsticks" : "Capsule", pi, conf->capsule_h[pi], conf->radius[pi]); delete h; return UD_ERR_INVALID;
       }
     }
     const double nrm = std::sqrt(n2);
@@ -629,7 +714,7 @@ int ud_plb_create(const ud_plb_conf* conf, ud_plb** out) {
   const bool mk_only = h->gen || !unit_scale;
   if (conf->path == 2 && mk_only) {
     ud::set_error("ud_plb_create: path = 2 (persistent) has no %s: such a handle runs the multi-kernel path (path = 0 or 1)",
-                  h->rot_state ? "rotating primitives (rot_state)" : h->shape ? "Box, Cylinder or Torus primitive (prim_kind = 3, 4, 5)" : h->gen ? "Capsule primitive (prim_kind = 1)" : "action_scale other than (1, 1, 1)");
+                  h->chop ? "Chopsticks primitive (prim_kind = 6)" : h->rot_state ? "rotating primitives (rot_state)" : h->shape ? "Box, Cylinder or Torus primitive (prim_kind = 3, 4, 5)" : h->gen ? "Capsule primitive (prim_kind = 1)" : "action_scale other than (1, 1, 1)");
     delete h; return UD_ERR_UNSUPPORTED;
   }
   h->G = (long)c.n_grid * c.n_grid * c.n_grid;
@@ -662,7 +747,7 @@ void ud_plb_destroy(ud_plb* h) {
 
 size_t ud_plb_ckpt_bytes(const ud_plb* h, int B) {
   if (!h || B < 1) return 0;
-  return h->cl.per > 0 ? plb_cluster_ckpt_bytes(h, B) : plb_ckpt_layout(h->c, B, h->rot_state).total;
+  return h->cl.per > 0 ? plb_cluster_ckpt_bytes(h, B) : plb_ckpt_layout(h->c, B, h->rot_state, h->chop).total;
 }
 
 int ud_plb_launch_plan(const ud_plb* h, int B) {
@@ -691,11 +776,13 @@ int ud_plb_poll_timeouts(ud_plb* h, void* stream) {
 
 }  // extern "C"
 
-// ud_plb_step_fwd (prim_rot == nullptr) and ud_plb_step_fwd_rot (a rot_state handle: prim_rot / prim_rot_out given)
+// ud_plb_step_fwd (prim_rot == nullptr), ud_plb_step_fwd_rot (a rot_state handle: prim_rot / prim_rot_out given) and ud_plb_step_fwd_gap (a Chopsticks
+// handle: prim_gap / prim_gap_out as well)
 static int plb_step_fwd_impl(const char* who, ud_plb* h, int B, const double* x, const double* v, const double* C, const double* F,
                              const double* prim_pos, const double* prim_rot, const double* softness, const double* action, const double* E,
                              const double* nu, const double* yield_stress, double* x_out, double* v_out, double* C_out,
-                             double* F_out, double* prim_pos_out, double* prim_rot_out, void* ckpt, void* stream) {
+                             double* F_out, double* prim_pos_out, double* prim_rot_out, void* ckpt, void* stream,
+                             const double* prim_gap = nullptr, double* prim_gap_out = nullptr) {
   if (B < 1) { ud::set_error("%s: B=%d", who, B); return UD_ERR_INVALID; }
   if (B > h->B) { ud::set_error("%s: B=%d exceeds the handle's max_envs=%d (arenas are sized at create)", who, B, h->B); return UD_ERR_INVALID; }
   const bool rot = prim_rot != nullptr;
@@ -720,10 +807,13 @@ static int plb_step_fwd_impl(const char* who, ud_plb* h, int B, const double* x,
   a.slots = 2; a.hs_in = 0; a.hs_out = 1; a.lb = 0; a.ls = 0; a.lprev = 1; a.lnext = 1; a.hs_out2 = 0; a.epoch2 = 0;
   a.ck_skip = 0; a.w.gck_cnt = nullptr; a.w.gck_lin = nullptr; a.w.gck_val = nullptr; a.w.svd = nullptr;
   ud::PlbRot rr = h->rot;
+  ud::PlbGap gg = h->gap;
+  const bool chop = prim_gap != nullptr;
   if (ckpt) {   // keep every substep's particle state, the primitive trajectory, the spatial order (and the touched grid cells) for ud_plb_step_bwd
     plb_bind_ckpt(a, h->c, B, ckpt);
     a.slots = h->c.S + 1;
     if (rot) rr.rot = (double*)((char*)ckpt + plb_ckpt_layout(h->c, B, true).rot);
+    if (chop) gg.gap = (double*)((char*)ckpt + plb_ckpt_layout(h->c, B, true, true).gap);
   }
   a.softness = softness; a.E = E; a.nu = nu; a.ys = yield_stress;
   const dim3 blk(256), gp((h->c.N + 255) / 256, B), gc((h->cap + 255) / 256, B);
@@ -732,7 +822,9 @@ static int plb_step_fwd_impl(const char* who, ud_plb* h, int B, const double* x,
   const int lanes = h->lanes ? h->lanes : (((long)B * h->c.N <= 16000) ? 8 : (((long)B * h->c.N < 100000) ? 4 : 1));
   const dim3 gq((lanes * h->c.N + 255) / 256, B);
   rr.ext = const_cast<double*>(prim_rot);
-  if (rot) hipLaunchKernelGGL(ud::plb_pack<true>, gp, blk, 0, st, a, x, v, C, F, sorted ? (const int*)h->order : (const int*)nullptr, prim_pos, action, h->ascale, ud::PlbRotArg<true>{rr});
+  gg.ext = const_cast<double*>(prim_gap); gg.ext_out = prim_gap_out;
+  if (chop) hipLaunchKernelGGL(ud::plb_pack_gap, gp, blk, 0, st, a, x, v, C, F, sorted ? (const int*)h->order : (const int*)nullptr, prim_pos, action, h->ascale, rr, gg);
+  else if (rot) hipLaunchKernelGGL(ud::plb_pack<true>, gp, blk, 0, st, a, x, v, C, F, sorted ? (const int*)h->order : (const int*)nullptr, prim_pos, action, h->ascale, ud::PlbRotArg<true>{rr});
   else hipLaunchKernelGGL(ud::plb_pack<false>, gp, blk, 0, st, a, x, v, C, F, sorted ? (const int*)h->order : (const int*)nullptr, prim_pos, action, h->ascale, ud::PlbRotArg<false>{});
   // Per substep: plb_grid(f), then ONE particle launch: g2p(f) -> p2g(f + 1) (plb_g2p_p2g); p2g(0) opens the step, g2p(S - 1) closes it.
   const bool fused = true;
@@ -750,7 +842,8 @@ static int plb_step_fwd_impl(const char* who, ud_plb* h, int B, const double* x,
   UD_PLB_LAUNCH(plb_p2g);
   for (int f = 0; f < S; ++f) {
     set(f);
-    if (rot && h->shape) hipLaunchKernelGGL(ud::plb_grid<4>, gc, blk, 0, st, a, ud::PlbPrimArg<4>{h->prim, rr, h->shp});
+    if (chop) hipLaunchKernelGGL(ud::plb_grid<5>, gc, blk, 0, st, a, ud::PlbPrimArg<5>{h->prim, rr, h->shp, gg});
+    else if (rot && h->shape) hipLaunchKernelGGL(ud::plb_grid<4>, gc, blk, 0, st, a, ud::PlbPrimArg<4>{h->prim, rr, h->shp});
     else if (h->shape) hipLaunchKernelGGL(ud::plb_grid<3>, gc, blk, 0, st, a, ud::PlbPrimArg<3>{h->prim, h->shp});
     else if (rot) hipLaunchKernelGGL(ud::plb_grid<2>, gc, blk, 0, st, a, ud::PlbPrimArg<2>{h->prim, rr});
     else if (h->gen) hipLaunchKernelGGL(ud::plb_grid<1>, gc, blk, 0, st, a, ud::PlbPrimArg<1>{h->prim});
@@ -799,8 +892,22 @@ int ud_plb_step_fwd_rot(ud_plb* h, int B, const double* x, const double* v, cons
     ud::set_error("ud_plb_step_fwd_rot: null argument"); return UD_ERR_INVALID;
   }
   if (!h->rot_state) { ud::set_error("ud_plb_step_fwd_rot: the handle was not created with rot_state (use ud_plb_step_fwd)"); return UD_ERR_INVALID; }
+  if (h->chop) { ud::set_error("ud_plb_step_fwd_rot: a Chopsticks handle (prim_kind[0] = 6) carries its gap as state and steps through ud_plb_step_fwd_gap"); return UD_ERR_INVALID; }
   return plb_step_fwd_impl("ud_plb_step_fwd_rot", h, B, x, v, C, F, prim_pos, prim_rot, softness, action, E, nu, yield_stress, x_out, v_out, C_out, F_out,
                            prim_pos_out, prim_rot_out, ckpt, stream);
+}
+
+int ud_plb_step_fwd_gap(ud_plb* h, int B, const double* x, const double* v, const double* C, const double* F,
+                        const double* prim_pos, const double* prim_rot, const double* prim_gap, const double* softness, const double* action,
+                        const double* E, const double* nu, const double* yield_stress, double* x_out, double* v_out, double* C_out,
+                        double* F_out, double* prim_pos_out, double* prim_rot_out, double* prim_gap_out, void* ckpt, void* stream) {
+  if (!h || !x || !v || !C || !F || !prim_pos || !prim_rot || !prim_gap || !softness || !action || !E || !nu || !yield_stress || !x_out || !v_out || !C_out ||
+      !F_out || !prim_pos_out || !prim_rot_out || !prim_gap_out) {
+    ud::set_error("ud_plb_step_fwd_gap: null argument"); return UD_ERR_INVALID;
+  }
+  if (!h->chop) { ud::set_error("ud_plb_step_fwd_gap: the handle has no Chopsticks (prim_kind[0] = 6): use ud_plb_step_fwd%s", h->rot_state ? "_rot" : ""); return UD_ERR_INVALID; }
+  return plb_step_fwd_impl("ud_plb_step_fwd_gap", h, B, x, v, C, F, prim_pos, prim_rot, softness, action, E, nu, yield_stress, x_out, v_out, C_out, F_out,
+                           prim_pos_out, prim_rot_out, ckpt, stream, prim_gap, prim_gap_out);
 }
 
 }  // extern "C"

@@ -26,7 +26,7 @@ namespace ud {
 
 // ---- grid op, kept: v_out of every touched cell into buffer 1 (buffer 0 keeps (m, mv)) ---------------------------------
 template <int GEN>   // 1: the handle has a general primitive (plb_prim.h); 2: a rot_state handle, the substep's quaternions read from pr.r.rot;
-                     // 3 / 4: a shape handle (Box, Cylinder, Torus) without / with rot_state
+                     // 3 / 4: a shape handle (Box, Cylinder, Torus) without / with rot_state; 5: a Chopsticks handle (gap[f] from pr.g.gap)
 __global__ void __launch_bounds__(256) plb_grid_keep(PlbArgs a, PlbPrimArg<GEN> pr) {
   const int b = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x;
   const PlbConst& c = a.c;
@@ -59,6 +59,9 @@ __global__ void __launch_bounds__(256) plb_grid_keep(PlbArgs a, PlbPrimArg<GEN> 
     cell = plb_buf(a, cur, b) + lin * 4;
   }
   double vv[3];
+  if constexpr (GEN == 5) plb_grid_cell_any<GEN>(c, pr, lin, cell[0], cell + 1, a.w.pos + ((long)b * (c.S + 1) + a.f) * c.np * 3, a.softness + b * c.np, vv,
+                                                 pr.r.rot + ((long)b * (c.S + 1) + a.f) * c.np * 4, pr.g.gap + ((long)b * (c.S + 1) + a.f) * c.np);
+  else
   if constexpr (GEN == 2 || GEN == 4) plb_grid_cell_any<GEN>(c, pr, lin, cell[0], cell + 1, a.w.pos + ((long)b * (c.S + 1) + a.f) * c.np * 3, a.softness + b * c.np, vv,
                                                  pr.r.rot + ((long)b * (c.S + 1) + a.f) * c.np * 4);
   else
@@ -182,7 +185,7 @@ __global__ void __launch_bounds__(256) plb_g2p_adj(PlbArgs a, int gs_in) {
 // ---- grid op adjoint (:200-232 in reverse), one touched cell per lane -------------------------------------------------
 template <int GEN>
 __global__ void __launch_bounds__(256) plb_grid_adj(PlbArgs a, PlbPrimArg<GEN> pr) {
-  constexpr bool ROT = GEN == 2 || GEN == 4;
+  constexpr bool ROT = GEN == 2 || GEN == 4 || GEN == 5;
   const int b = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x;
   const PlbConst& c = a.c;
   // per-env cotangents (sticky-sphere positions, ground friction): summed over the wave, one atomic per wave and word -- one per cell
@@ -190,6 +193,7 @@ __global__ void __launch_bounds__(256) plb_grid_adj(PlbArgs a, PlbPrimArg<GEN> p
   double qs[2][3] = {{0, 0, 0}, {0, 0, 0}}, gfric = 0;
   [[maybe_unused]] double q0[2][3] = {{0, 0, 0}, {0, 0, 0}};   // GEN: what the cell sends to gpos[f], independent of qs
   [[maybe_unused]] double gr0[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, gr1[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};   // ROT: ... to grot[f] / grot[f + 1]
+  [[maybe_unused]] double gg[2] = {0, 0};                        // GEN == 5: ... to ggap[f]
   const bool inlist = t < min(a.w.count[a.lb * a.B + b], a.cap);
   const long lin = inlist ? a.w.list[((long)a.lb * a.B + b) * a.cap + t] : 0;
   const double* cell = plb_buf(a, a.lb, b) + lin * 4;
@@ -197,9 +201,12 @@ __global__ void __launch_bounds__(256) plb_grid_adj(PlbArgs a, PlbPrimArg<GEN> p
   if (inlist) {
     const double g[3] = {ga[0], ga[1], ga[2]};
     double gout[4];
-    if constexpr (GEN == 4) plb_grid_cell_adj_gen<true, true>(c, pr.p, lin, cell[0], cell + 1, g, a.w.pos + ((long)b * (c.S + 1) + a.f) * c.np * 3, a.softness + b * c.np, gout, q0, qs, gfric,
+    if constexpr (GEN == 5) plb_grid_cell_adj_gen<true, 2>(c, pr.p, lin, cell[0], cell + 1, g, a.w.pos + ((long)b * (c.S + 1) + a.f) * c.np * 3, a.softness + b * c.np, gout, q0, qs,
+                                                           gfric, pr.r.rot + ((long)b * (c.S + 1) + a.f) * c.np * 4, gr0, gr1, &pr.s, gg,
+                                                           pr.g.gap + ((long)b * (c.S + 1) + a.f) * c.np);
+    else if constexpr (GEN == 4) plb_grid_cell_adj_gen<true, 1>(c, pr.p, lin, cell[0], cell + 1, g, a.w.pos + ((long)b * (c.S + 1) + a.f) * c.np * 3, a.softness + b * c.np, gout, q0, qs, gfric,
                                                               pr.r.rot + ((long)b * (c.S + 1) + a.f) * c.np * 4, gr0, gr1, &pr.s);
-    else if constexpr (GEN == 3) plb_grid_cell_adj_gen<false, true>(c, pr.p, lin, cell[0], cell + 1, g, a.w.pos + ((long)b * (c.S + 1) + a.f) * c.np * 3, a.softness + b * c.np, gout, q0, qs,
+    else if constexpr (GEN == 3) plb_grid_cell_adj_gen<false, 1>(c, pr.p, lin, cell[0], cell + 1, g, a.w.pos + ((long)b * (c.S + 1) + a.f) * c.np * 3, a.softness + b * c.np, gout, q0, qs,
                                                                     gfric, nullptr, nullptr, nullptr, &pr.s);
     else
     if constexpr (ROT) plb_grid_cell_adj_gen<true>(c, pr.p, lin, cell[0], cell + 1, g, a.w.pos + ((long)b * (c.S + 1) + a.f) * c.np * 3, a.softness + b * c.np, gout, q0, qs, gfric,
@@ -223,6 +230,12 @@ __global__ void __launch_bounds__(256) plb_grid_adj(PlbArgs a, PlbPrimArg<GEN> p
           if (lead && s0 != 0.0) atomicAdd(grot + k, s0);
           if (lead && s1 != 0.0) atomicAdd(grot + c.np * 4 + k, s1);
         }
+      }
+    }
+    if constexpr (GEN == 5) {      // the gap cotangent likewise
+      if (__any(gg[pi] != 0.0)) {
+        const double sg = plb_wave_sum(gg[pi]);
+        if (lead && sg != 0.0) atomicAdd(pr.g.ggap + ((long)b * (c.S + 1) + a.f) * c.np + pi, sg);
       }
     }
     if constexpr (GEN != 0) {
@@ -354,6 +367,18 @@ __global__ void plb_adj_reset_counts(PlbArgs a) {
   if (b < a.Bcall) { a.w.count[b] = 0; a.w.count[a.B + b] = 0; }
 }
 
+// one particle's output cotangents into the gstate slot, through the checkpoint's spatial order
+__device__ __forceinline__ void plb_adj_pack_particle(const PlbArgs& a, int b, int p, int slot, const double* gx, const double* gv, const double* gC, const double* gF) {
+  const PlbConst& c = a.c;
+  double* g = a.w.gstate + ((long)b * 2 + slot) * 24 * c.Np;
+  const int up = a.w.perm[(long)b * c.Np + p];
+  const long o3 = ((long)b * c.N + up) * 3, o9 = ((long)b * c.N + up) * 9;
+#pragma unroll
+  for (int d = 0; d < 3; ++d) { g[d * c.Np + p] = gx ? gx[o3 + d] : 0.0; g[(3 + d) * c.Np + p] = gv ? gv[o3 + d] : 0.0; }
+#pragma unroll
+  for (int d = 0; d < 9; ++d) { g[(6 + d) * c.Np + p] = gC ? gC[o9 + d] : 0.0; g[(15 + d) * c.Np + p] = gF ? gF[o9 + d] : 0.0; }
+}
+
 // cotangent of the step outputs -> gstate slot (in the spatial order of the checkpoint); zero the accumulators
 template <bool ROT>   // a rot_state handle: also the rotation cotangents (rr.r.grot; g_prim_rot = rr.r.ext, may be null)
 __global__ void __launch_bounds__(256) plb_adj_pack(PlbArgs a, int slot, const double* gx, const double* gv, const double* gC, const double* gF, const double* gpp,
@@ -370,13 +395,7 @@ __global__ void __launch_bounds__(256) plb_adj_pack(PlbArgs a, int slot, const d
     if (threadIdx.x < 4) a.w.gpar[b * 4 + threadIdx.x] = 0.0;
   }
   if (p >= c.N) return;
-  double* g = a.w.gstate + ((long)b * 2 + slot) * 24 * c.Np;
-  const int up = a.w.perm[(long)b * c.Np + p];
-  const long o3 = ((long)b * c.N + up) * 3, o9 = ((long)b * c.N + up) * 9;
-#pragma unroll
-  for (int d = 0; d < 3; ++d) { g[d * c.Np + p] = gx ? gx[o3 + d] : 0.0; g[(3 + d) * c.Np + p] = gv ? gv[o3 + d] : 0.0; }
-#pragma unroll
-  for (int d = 0; d < 9; ++d) { g[(6 + d) * c.Np + p] = gC ? gC[o9 + d] : 0.0; g[(15 + d) * c.Np + p] = gF ? gF[o9 + d] : 0.0; }
+  plb_adj_pack_particle(a, b, p, slot, gx, gv, gC, gF);
 }
 
 __global__ void __launch_bounds__(256) plb_adj_unpack(PlbArgs a, int slot, double* gx, double* gv, double* gC, double* gF) {
@@ -504,6 +523,83 @@ __global__ void __launch_bounds__(64) plb_adj_epilogue_rot(PlbArgs a, PlbRot r, 
   if (g_fric) g_fric[b] = a.w.gpar[b * 4 + 3];
 }
 
+// The same for a Chopsticks handle (r.kin == 3): plb_adj_pack<true> with the gap cotangents seeded from g_prim_gap (g.ext, may be null) ...
+__global__ void __launch_bounds__(256) plb_adj_pack_gap(PlbArgs a, int slot, const double* gx, const double* gv, const double* gC, const double* gF, const double* gpp,
+                                                        PlbRot r, PlbGap g) {
+  const int b = blockIdx.y, p = blockIdx.x * blockDim.x + threadIdx.x;
+  const PlbConst& c = a.c;
+  if (blockIdx.x == 0) {
+    for (int e = threadIdx.x; e < (c.S + 1) * c.np; e += blockDim.x)
+      g.ggap[(long)b * (c.S + 1) * c.np + e] = (g.ext && e >= c.S * c.np) ? g.ext[(long)b * c.np + e - c.S * c.np] : 0.0;
+    for (int e = threadIdx.x; e < (c.S + 1) * c.np * 4; e += blockDim.x)
+      r.grot[(long)b * (c.S + 1) * c.np * 4 + e] = (r.ext && e >= c.S * c.np * 4) ? r.ext[(long)b * c.np * 4 + e - c.S * c.np * 4] : 0.0;
+    for (int e = threadIdx.x; e < (c.S + 1) * c.np * 3; e += blockDim.x)
+      a.w.gpos[(long)b * (c.S + 1) * c.np * 3 + e] = (gpp && e >= c.S * c.np * 3) ? gpp[(long)b * c.np * 3 + e - c.S * c.np * 3] : 0.0;
+    if (threadIdx.x < 4) a.w.gpar[b * 4 + threadIdx.x] = 0.0;
+  }
+  if (p >= c.N) return;
+  plb_adj_pack_particle(a, b, p, slot, gx, gv, gC, gF);
+}
+// ... and plb_adj_epilogue_rot through the adjoint of plb_kinematics_gap (plb.hip): f = S - 1 ... 0 through the position clamp, the right-multiplied
+// rotation step and max(gap - gap_vel, minimal_gap), whose cotangent passes to gap[f] and -gap_vel where gap[f] - gap_vel > minimal_gap and is zero
+// where it is smaller -- from gpos / grot / ggap to g_prim_pos0, g_prim_rot0, g_prim_gap0 [B,np] and g_action [B,7].
+__global__ void __launch_bounds__(64) plb_adj_epilogue_gap(PlbArgs a, PlbRot r, PlbGap gp, PlbScale sc, const double* action, double* g_prim_pos0, double* g_prim_rot0,
+                                                           double* g_prim_gap0, double* g_action, double* g_E, double* g_nu, double* g_ys, double* g_fric) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= a.Bcall) return;   // g_action, g_prim_gap0, ... are the caller's [Bcall] arrays
+  const PlbConst& c = a.c;
+  const double* P = a.w.pos + (long)b * (c.S + 1) * c.np * 3;
+  double* G = a.w.gpos + (long)b * (c.S + 1) * c.np * 3;
+  const double* R = r.rot + (long)b * (c.S + 1) * c.np * 4;
+  double* GR = r.grot + (long)b * (c.S + 1) * c.np * 4;
+  const double* GP = gp.gap + (long)b * (c.S + 1) * c.np;
+  double* GG = gp.ggap + (long)b * (c.S + 1) * c.np;
+  for (int pi = 0; pi < c.np; ++pi) {
+    double raw[7] = {0, 0, 0, 0, 0, 0, 0}, av[7] = {0, 0, 0, 0, 0, 0, 0}, gav[7] = {0, 0, 0, 0, 0, 0, 0};
+    if (pi == 0) {
+#pragma unroll
+      for (int d = 0; d < 7; ++d) {
+        raw[d] = action[(long)b * 7 + d];
+        av[d] = fmin(fmax(raw[d], -1.0), 1.0) * (d < 3 ? sc.s[d] : (d < 6 ? r.sw[d - 3] : gp.sg)) / (double)c.S;
+      }
+    }
+    double dq[4], gdq[4] = {0, 0, 0, 0};
+    plb_w2quat(av + 3, dq);
+    for (int s = c.S - 1; s >= 0; --s) {
+      double gq[4] = {0, 0, 0, 0};
+      if (pi == 0) {
+        plb_qstep_right_adj(R + (s * c.np + pi) * 4, dq, GR + ((s + 1) * c.np + pi) * 4, gq, gdq);
+        plb_gap_step_adj(GP[s * c.np + pi], av[6], gp.mingap[pi], GG[(s + 1) * c.np + pi], GG[s * c.np + pi], gav[6]);
+      } else {
+        plb_qmul_adj(dq, R + (s * c.np + pi) * 4, GR + ((s + 1) * c.np + pi) * 4, gdq, gq);
+        GG[s * c.np + pi] += GG[(s + 1) * c.np + pi];
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) GR[(s * c.np + pi) * 4 + k] += gq[k];
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        const double un = P[(s * c.np + pi) * 3 + d] + av[d];
+        const double g = (un >= c.lo[d] && un <= c.hi[d]) ? G[((s + 1) * c.np + pi) * 3 + d] : 0.0;
+        G[(s * c.np + pi) * 3 + d] += g;
+        gav[d] += g;
+      }
+    }
+    plb_w2quat_adj(av + 3, gdq, gav + 3);
+    for (int d = 0; d < 3; ++d)
+      if (g_prim_pos0) g_prim_pos0[((long)b * c.np + pi) * 3 + d] = G[pi * 3 + d];
+    for (int k = 0; k < 4; ++k)
+      if (g_prim_rot0) g_prim_rot0[((long)b * c.np + pi) * 4 + k] = GR[pi * 4 + k];
+    if (g_prim_gap0) g_prim_gap0[(long)b * c.np + pi] = GG[pi];
+    if (pi == 0 && g_action)
+      for (int d = 0; d < 7; ++d)
+        g_action[(long)b * 7 + d] = (raw[d] >= -1.0 && raw[d] <= 1.0) ? gav[d] * (d < 3 ? sc.s[d] : (d < 6 ? r.sw[d - 3] : gp.sg)) / (double)c.S : 0.0;
+  }
+  if (g_E) g_E[b] = a.w.gpar[b * 4];
+  if (g_nu) g_nu[b] = a.w.gpar[b * 4 + 1];
+  if (g_ys) g_ys[b] = a.w.gpar[b * 4 + 2];
+  if (g_fric) g_fric[b] = a.w.gpar[b * 4 + 3];
+}
+
 // ---- losses (engine/losses/loss.py) -----------------------------------------------------------------------------------
 // grid mass of the particles (compute_grid_m_kernel): dense [B][G], zeroed by the caller
 __global__ void __launch_bounds__(256) plb_loss_mass(PlbConst c, long G, const double* x, double* gm) {
@@ -552,10 +648,32 @@ __global__ void __launch_bounds__(256) plb_loss_grid(long G, const double* gm, c
 // grad / den (the sphere's is left as the quotient the callers have always formed: d / len)
 // ROT (a rot_state handle): the Capsule's distance in the frame of q, this env's current rotation of the primitive; gq (with grad; may be null):
 // the gradient of the distance in q, through the inverse with its normalisation
+// GEN == 5 (a Chopsticks handle): gap = the env's current gaps [np]; ggap (with grad; may be null): the gradient of the distance in gap[pi]
 template <int GEN>
 __device__ __forceinline__ double plb_loss_dist(const PlbConst& c, const PlbPrimArg<GEN>& pr, int pi, const double* xp, const double* pp, double* grad, double* den,
-                                                const double* q = nullptr, double* gq = nullptr) {
+                                                const double* q = nullptr, double* gq = nullptr, const double* gap = nullptr, double* ggap = nullptr) {
   const double d[3] = {xp[0] - pp[0], xp[1] - pp[1], xp[2] - pp[2]};
+  if constexpr (GEN == 5) {                  // as GEN == 4 below, through the shape layer with the gap beside the constants
+    if (pr.p.kind[pi] != 0) {
+      double qi[4], pl[3];
+      plb_qinv(q, qi);
+      const double dist = plb_shape_local<true, 2>(pr.p, pr.s, pi, c.radius[pi], d, pl, qi, gap);
+      if (grad) {
+        const double zero[3] = {0, 0, 0};
+        double g[3], gg;
+        plb_shape_local_adj<true, 2>(pr.p, pr.s, pi, pl, 1.0, zero, zero, grad, qi, g, &gg, gap);
+        *den = 1.0;
+        if (ggap) *ggap = gg;
+        if (gq) {
+          double gqi[4];
+          plb_qrot_adj_rot(qi, d, g, gqi);
+          gq[0] = 0.0; gq[1] = 0.0; gq[2] = 0.0; gq[3] = 0.0;
+          plb_qinv_adj(q, qi, gqi, gq);
+        }
+      }
+      return dist;
+    }
+  } else
   if constexpr (GEN == 3 || GEN == 4) {      // a shape handle: the kind's own sdf through the shape layer, its gradient the layer's adjoint of the distance alone
     if (pr.p.kind[pi] != 0) {
       constexpr bool ROT = GEN == 4;
@@ -617,7 +735,8 @@ __device__ __forceinline__ double plb_loss_dist(const PlbConst& c, const PlbPrim
   return len - c.radius[pi];
 }
 
-template <int GEN>   // 2: a rot_state handle, the primitive's current rotation per env in pr.r.rot [B][np][4]; 3 / 4: a shape handle without / with it
+template <int GEN>   // 2: a rot_state handle, the primitive's current rotation per env in pr.r.rot [B][np][4]; 3 / 4: a shape handle without / with it;
+                     // 5: a Chopsticks handle, the current gap per env in pr.g.gap [B][np] as well
 __global__ void __launch_bounds__(256) plb_loss_contact(PlbConst c, PlbPrimArg<GEN> pr, const double* x, const double* prim_pos, int soft, double* lred) {
   __shared__ double sh[4];
   const int b = blockIdx.y, p = blockIdx.x * blockDim.x + threadIdx.x;
@@ -626,7 +745,8 @@ __global__ void __launch_bounds__(256) plb_loss_contact(PlbConst c, PlbPrimArg<G
     if (p < c.N) {
       const double* xp = x + ((long)b * c.N + p) * 3;
       const double* pp = prim_pos + ((long)b * c.np + pi) * 3;
-      if constexpr (GEN == 2 || GEN == 4) dij = fmax(plb_loss_dist<GEN>(c, pr, pi, xp, pp, nullptr, nullptr, pr.r.rot + ((long)b * c.np + pi) * 4), 0.0);
+      if constexpr (GEN == 5) dij = fmax(plb_loss_dist<GEN>(c, pr, pi, xp, pp, nullptr, nullptr, pr.r.rot + ((long)b * c.np + pi) * 4, nullptr, pr.g.gap + (long)b * c.np), 0.0);
+      else if constexpr (GEN == 2 || GEN == 4) dij = fmax(plb_loss_dist<GEN>(c, pr, pi, xp, pp, nullptr, nullptr, pr.r.rot + ((long)b * c.np + pi) * 4), 0.0);
       else dij = fmax(plb_loss_dist<GEN>(c, pr, pi, xp, pp, nullptr, nullptr), 0.0);
       sw = 1.0 / (1.0 + dij * dij * 10000.0);
     }
@@ -659,11 +779,11 @@ __global__ void plb_loss_finish(PlbConst c, int B, int soft, const double* wts, 
 
 // loss adjoint: g_x and g_prim_pos.  Needs gm (grid mass) and lred (the forward's sums) of the same inputs.
 // ROT: every lane of a wave stays (a lane past the last particle repeats it and sends nothing), for the wave sums of the rotation cotangent
-template <int GEN>   // 2: prim_rot in pr.r.rot, g_prim_rot in pr.r.grot (may be null)
+template <int GEN>   // 2: prim_rot in pr.r.rot, g_prim_rot in pr.r.grot (may be null); 5: also prim_gap in pr.g.gap, g_prim_gap in pr.g.ggap (may be null)
 __global__ void __launch_bounds__(256) plb_loss_bwd_kernel(PlbConst c, PlbPrimArg<GEN> pr, long G, int soft, const double* wts, const double* x, const double* prim_pos,
                                                           const double* td, const double* tsdf, const double* gm, const double* lred,
                                                           const double* g_loss, double* g_x, double* g_pp) {
-  constexpr bool ROT = GEN == 2 || GEN == 4;
+  constexpr bool ROT = GEN == 2 || GEN == 4 || GEN == 5;
   [[maybe_unused]] const double* prim_rot = nullptr;
   [[maybe_unused]] double* g_pr = nullptr;
   if constexpr (ROT) { prim_rot = pr.r.rot; g_pr = pr.r.grot; }
@@ -696,7 +816,10 @@ __global__ void __launch_bounds__(256) plb_loss_bwd_kernel(PlbConst c, PlbPrimAr
     const double* pp = prim_pos + ((long)b * c.np + pi) * 3;
     double dn[3], len;   // gradient of the distance in x: dn / len
     [[maybe_unused]] double gq[4] = {0, 0, 0, 0}, gqs[4] = {0, 0, 0, 0};
+    [[maybe_unused]] double gg = 0, ggs = 0;
     double raw;
+    if constexpr (GEN == 5) raw = plb_loss_dist<GEN>(c, pr, pi, xp, pp, dn, &len, prim_rot + ((long)b * c.np + pi) * 4, gq, pr.g.gap + (long)b * c.np, &gg);
+    else
     if constexpr (ROT) raw = plb_loss_dist<GEN>(c, pr, pi, xp, pp, dn, &len, prim_rot + ((long)b * c.np + pi) * 4, gq);
     else raw = plb_loss_dist<GEN>(c, pr, pi, xp, pp, dn, &len);
     const double dij = fmax(raw, 0.0);
@@ -719,14 +842,21 @@ __global__ void __launch_bounds__(256) plb_loss_bwd_kernel(PlbConst c, PlbPrimAr
 #pragma unroll
         for (int k = 0; k < 4; ++k) gqs[k] = gd * gq[k];
       }
+      if constexpr (GEN == 5) ggs = gd * gg;
     }
     if constexpr (ROT) {      // wave sum behind a wave-uniform test, one atomic per wave and word (as plb_grid_adj)
-      if (g_pr && plb_general<GEN == 4>(pr.p.kind[pi]) && __any(gqs[0] != 0.0 || gqs[1] != 0.0 || gqs[2] != 0.0 || gqs[3] != 0.0)) {
+      if (g_pr && plb_general<(GEN == 4 || GEN == 5) ? 1 : 0>(pr.p.kind[pi]) && __any(gqs[0] != 0.0 || gqs[1] != 0.0 || gqs[2] != 0.0 || gqs[3] != 0.0)) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           const double sm = plb_wave_sum(gqs[k]);
           if ((threadIdx.x & 63) == 0 && sm != 0.0) atomicAdd(g_pr + ((long)b * c.np + pi) * 4 + k, sm);
         }
+      }
+    }
+    if constexpr (GEN == 5) {      // the gap cotangent, reduced the same way
+      if (pr.g.ggap && __any(ggs != 0.0)) {
+        const double sm = plb_wave_sum(ggs);
+        if ((threadIdx.x & 63) == 0 && sm != 0.0) atomicAdd(pr.g.ggap + (long)b * c.np + pi, sm);
       }
     }
   }
@@ -741,11 +871,12 @@ __global__ void __launch_bounds__(256) plb_loss_bwd_kernel(PlbConst c, PlbPrimAr
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-// ud_plb_step_bwd (rot == false) and ud_plb_step_bwd_rot (a rot_state handle)
+// ud_plb_step_bwd (rot == false), ud_plb_step_bwd_rot (a rot_state handle) and ud_plb_step_bwd_gap (chop: a Chopsticks handle)
 static int plb_step_bwd_impl(const char* who, bool rot, ud_plb* h, int B, const void* ckpt, const double* softness, const double* action, const double* E, const double* nu,
                              const double* yield_stress, const double* g_x, const double* g_v, const double* g_C, const double* g_F,
                              const double* g_prim_pos, const double* g_prim_rot, double* g_x0, double* g_v0, double* g_C0, double* g_F0, double* g_prim_pos0,
-                             double* g_prim_rot0, double* g_action, double* g_E, double* g_nu, double* g_yield_stress, double* g_ground_friction, void* stream) {
+                             double* g_prim_rot0, double* g_action, double* g_E, double* g_nu, double* g_yield_stress, double* g_ground_friction, void* stream,
+                             bool chop = false, const double* g_prim_gap = nullptr, double* g_prim_gap0 = nullptr) {
   if (B < 1) { ud::set_error("%s: B=%d", who, B); return UD_ERR_INVALID; }
   if (B > h->B) { ud::set_error("%s: B=%d exceeds the handle's max_envs=%d", who, B, h->B); return UD_ERR_INVALID; }
   hipStream_t st = (hipStream_t)stream;
@@ -758,6 +889,9 @@ static int plb_step_bwd_impl(const char* who, bool rot, ud_plb* h, int B, const 
   plb_bind_ckpt(a, h->c, B, const_cast<void*>(ckpt));
   ud::PlbRot rr = h->rot;
   if (rot) rr.rot = (double*)((char*)const_cast<void*>(ckpt) + plb_ckpt_layout(h->c, B, true).rot);
+  ud::PlbGap gg = h->gap;
+  if (chop) gg.gap = (double*)((char*)const_cast<void*>(ckpt) + plb_ckpt_layout(h->c, B, true, true).gap);
+  gg.ext = const_cast<double*>(g_prim_gap); gg.ext_out = nullptr;
   a.slots = h->c.S + 1; a.lb = 0; a.ls = 0; a.lprev = 1; a.lnext = 1; a.hs_out2 = 0; a.epoch2 = 0;
   a.ck_skip = h->c.gck > 0 ? 1 : 0;
   const bool never_recompute = h->c.gck >= h->cap;          // every substep of every env is in the grid checkpoint: no recompute launch at all
@@ -767,7 +901,8 @@ static int plb_step_bwd_impl(const char* who, bool rot, ud_plb* h, int B, const 
   const dim3 gq((lanes * h->c.N + 255) / 256, B), gqa((lanes * h->c.N + 127) / 128, B);
   hipLaunchKernelGGL(ud::plb_adj_reset_counts, dim3((B + 63) / 64), dim3(64), 0, st, a);
   rr.ext = const_cast<double*>(g_prim_rot);
-  if (rot) hipLaunchKernelGGL(ud::plb_adj_pack<true>, gp, blk, 0, st, a, S & 1, g_x, g_v, g_C, g_F, g_prim_pos, ud::PlbRotArg<true>{rr});
+  if (chop) hipLaunchKernelGGL(ud::plb_adj_pack_gap, gp, blk, 0, st, a, S & 1, g_x, g_v, g_C, g_F, g_prim_pos, rr, gg);
+  else if (rot) hipLaunchKernelGGL(ud::plb_adj_pack<true>, gp, blk, 0, st, a, S & 1, g_x, g_v, g_C, g_F, g_prim_pos, ud::PlbRotArg<true>{rr});
   else hipLaunchKernelGGL(ud::plb_adj_pack<false>, gp, blk, 0, st, a, S & 1, g_x, g_v, g_C, g_F, g_prim_pos, ud::PlbRotArg<false>{});
   // Five launches per reverse substep.  List and (m, mv) buffer alternate with the substep like the forward's: plb_grid_keep retires
   // the cells of substep f + 1 (their buffer and cotangent cells back to zero) beside its own work, plb_g2p_adj resets that list's
@@ -775,7 +910,8 @@ static int plb_step_bwd_impl(const char* who, bool rot, ud_plb* h, int B, const 
   for (int f = S - 1; f >= 0; --f) {
     a.f = f; a.epoch = h->epoch++; a.hs_in = f; a.hs_out = f + 1; a.lb = f & 1; a.ls = a.lb; a.lprev = a.lb ^ 1; a.lnext = a.lprev;
     if (!never_recompute) ud::plb_launch_p2g(a, lanes, lanes > 1 ? gq : gp, st);   // recompute (m, mv) (rewrites F[f + 1] with the same values); envs with a checkpointed substep leave at once
-    if (rot && h->shape) hipLaunchKernelGGL(ud::plb_grid_keep<4>, gc, blk, 0, st, a, ud::PlbPrimArg<4>{h->prim, rr, h->shp});
+    if (chop) hipLaunchKernelGGL(ud::plb_grid_keep<5>, gc, blk, 0, st, a, ud::PlbPrimArg<5>{h->prim, rr, h->shp, gg});
+    else if (rot && h->shape) hipLaunchKernelGGL(ud::plb_grid_keep<4>, gc, blk, 0, st, a, ud::PlbPrimArg<4>{h->prim, rr, h->shp});
     else if (h->shape) hipLaunchKernelGGL(ud::plb_grid_keep<3>, gc, blk, 0, st, a, ud::PlbPrimArg<3>{h->prim, h->shp});
     else if (rot) hipLaunchKernelGGL(ud::plb_grid_keep<2>, gc, blk, 0, st, a, ud::PlbPrimArg<2>{h->prim, rr});
     else if (h->gen) hipLaunchKernelGGL(ud::plb_grid_keep<1>, gc, blk, 0, st, a, ud::PlbPrimArg<1>{h->prim});
@@ -783,7 +919,8 @@ static int plb_step_bwd_impl(const char* who, bool rot, ud_plb* h, int B, const 
     if (lanes == 8) hipLaunchKernelGGL(ud::plb_g2p_adj<8>, gq, blk, 0, st, a, (f + 1) & 1);
     else if (lanes == 4) hipLaunchKernelGGL(ud::plb_g2p_adj<4>, gq, blk, 0, st, a, (f + 1) & 1);
     else hipLaunchKernelGGL(ud::plb_g2p_adj<1>, gp, blk, 0, st, a, (f + 1) & 1);
-    if (rot && h->shape) hipLaunchKernelGGL(ud::plb_grid_adj<4>, gc, blk, 0, st, a, ud::PlbPrimArg<4>{h->prim, rr, h->shp});
+    if (chop) hipLaunchKernelGGL(ud::plb_grid_adj<5>, gc, blk, 0, st, a, ud::PlbPrimArg<5>{h->prim, rr, h->shp, gg});
+    else if (rot && h->shape) hipLaunchKernelGGL(ud::plb_grid_adj<4>, gc, blk, 0, st, a, ud::PlbPrimArg<4>{h->prim, rr, h->shp});
     else if (h->shape) hipLaunchKernelGGL(ud::plb_grid_adj<3>, gc, blk, 0, st, a, ud::PlbPrimArg<3>{h->prim, h->shp});
     else if (rot) hipLaunchKernelGGL(ud::plb_grid_adj<2>, gc, blk, 0, st, a, ud::PlbPrimArg<2>{h->prim, rr});
     else if (h->gen) hipLaunchKernelGGL(ud::plb_grid_adj<1>, gc, blk, 0, st, a, ud::PlbPrimArg<1>{h->prim});
@@ -796,7 +933,9 @@ static int plb_step_bwd_impl(const char* who, bool rot, ud_plb* h, int B, const 
   hipLaunchKernelGGL(ud::plb_adj_clear, gc, blk, 0, st, a);
   hipLaunchKernelGGL(ud::plb_adj_reset_counts, dim3((B + 63) / 64), dim3(64), 0, st, a);
   hipLaunchKernelGGL(ud::plb_adj_unpack, gp, blk, 0, st, a, 0, g_x0, g_v0, g_C0, g_F0);
-  if (rot) hipLaunchKernelGGL(ud::plb_adj_epilogue_rot, dim3((B + 63) / 64), dim3(64), 0, st, a, rr, h->ascale, action, g_prim_pos0, g_prim_rot0, g_action, g_E, g_nu,
+  if (chop) hipLaunchKernelGGL(ud::plb_adj_epilogue_gap, dim3((B + 63) / 64), dim3(64), 0, st, a, rr, gg, h->ascale, action, g_prim_pos0, g_prim_rot0, g_prim_gap0, g_action,
+                               g_E, g_nu, g_yield_stress, g_ground_friction);
+  else if (rot) hipLaunchKernelGGL(ud::plb_adj_epilogue_rot, dim3((B + 63) / 64), dim3(64), 0, st, a, rr, h->ascale, action, g_prim_pos0, g_prim_rot0, g_action, g_E, g_nu,
                               g_yield_stress, g_ground_friction);
   else hipLaunchKernelGGL(ud::plb_adj_epilogue, dim3((B + 63) / 64), dim3(64), 0, st, a, h->ascale, action, g_prim_pos0, g_action, g_E, g_nu, g_yield_stress, g_ground_friction);
   hipError_t e = hipGetLastError();
@@ -826,14 +965,28 @@ int ud_plb_step_bwd_rot(ud_plb* h, int B, const void* ckpt, const double* softne
     ud::set_error("ud_plb_step_bwd_rot: null argument"); return UD_ERR_INVALID;
   }
   if (!h->rot_state) { ud::set_error("ud_plb_step_bwd_rot: the handle was not created with rot_state (use ud_plb_step_bwd)"); return UD_ERR_INVALID; }
+  if (h->chop) { ud::set_error("ud_plb_step_bwd_rot: a Chopsticks handle (prim_kind[0] = 6) carries its gap as state and goes through ud_plb_step_bwd_gap"); return UD_ERR_INVALID; }
   return plb_step_bwd_impl("ud_plb_step_bwd_rot", true, h, B, ckpt, softness, action, E, nu, yield_stress, g_x, g_v, g_C, g_F, g_prim_pos, g_prim_rot, g_x0, g_v0,
                            g_C0, g_F0, g_prim_pos0, g_prim_rot0, g_action, g_E, g_nu, g_yield_stress, g_ground_friction, stream);
+}
+
+int ud_plb_step_bwd_gap(ud_plb* h, int B, const void* ckpt, const double* softness, const double* action, const double* E, const double* nu,
+                        const double* yield_stress, const double* g_x, const double* g_v, const double* g_C, const double* g_F,
+                        const double* g_prim_pos, const double* g_prim_rot, const double* g_prim_gap, double* g_x0, double* g_v0, double* g_C0, double* g_F0,
+                        double* g_prim_pos0, double* g_prim_rot0, double* g_prim_gap0, double* g_action, double* g_E, double* g_nu, double* g_yield_stress,
+                        double* g_ground_friction, void* stream) {
+  if (!h || !ckpt || !softness || !action || !E || !nu || !yield_stress || !g_x0 || !g_v0 || !g_C0 || !g_F0) {
+    ud::set_error("ud_plb_step_bwd_gap: null argument"); return UD_ERR_INVALID;
+  }
+  if (!h->chop) { ud::set_error("ud_plb_step_bwd_gap: the handle has no Chopsticks (prim_kind[0] = 6): use ud_plb_step_bwd%s", h->rot_state ? "_rot" : ""); return UD_ERR_INVALID; }
+  return plb_step_bwd_impl("ud_plb_step_bwd_gap", true, h, B, ckpt, softness, action, E, nu, yield_stress, g_x, g_v, g_C, g_F, g_prim_pos, g_prim_rot, g_x0, g_v0,
+                           g_C0, g_F0, g_prim_pos0, g_prim_rot0, g_action, g_E, g_nu, g_yield_stress, g_ground_friction, stream, true, g_prim_gap, g_prim_gap0);
 }
 
 }  // extern "C"
 
 static int plb_loss_common(ud_plb* h, int B, const double* x, const double* prim_pos, const double* prim_rot, const double* target_density, const double* target_sdf,
-                           const double* weights, int soft_contact, hipStream_t st) {
+                           const double* weights, int soft_contact, hipStream_t st, const double* prim_gap = nullptr) {
   if (B > h->B) { ud::set_error("ud_plb_loss: B=%d exceeds the handle's max_envs=%d", B, h->B); return UD_ERR_INVALID; }
   const ud::PlbConst& c = h->c;
   hipError_t e = hipMemsetAsync(h->gm, 0, (size_t)B * h->G * 8, st);
@@ -846,7 +999,10 @@ static int plb_loss_common(ud_plb* h, int B, const double* x, const double* prim
   if (c.np > 0) {
     ud::PlbRot rr = h->rot;
     rr.rot = const_cast<double*>(prim_rot); rr.grot = nullptr;
-    if (prim_rot && h->shape) hipLaunchKernelGGL(ud::plb_loss_contact<4>, gp, blk, 0, st, c, ud::PlbPrimArg<4>{h->prim, rr, h->shp}, x, prim_pos, soft_contact, h->lred);
+    ud::PlbGap gg = h->gap;
+    gg.gap = const_cast<double*>(prim_gap); gg.ggap = nullptr;
+    if (prim_gap) hipLaunchKernelGGL(ud::plb_loss_contact<5>, gp, blk, 0, st, c, ud::PlbPrimArg<5>{h->prim, rr, h->shp, gg}, x, prim_pos, soft_contact, h->lred);
+    else if (prim_rot && h->shape) hipLaunchKernelGGL(ud::plb_loss_contact<4>, gp, blk, 0, st, c, ud::PlbPrimArg<4>{h->prim, rr, h->shp}, x, prim_pos, soft_contact, h->lred);
     else if (h->shape) hipLaunchKernelGGL(ud::plb_loss_contact<3>, gp, blk, 0, st, c, ud::PlbPrimArg<3>{h->prim, h->shp}, x, prim_pos, soft_contact, h->lred);
     else if (prim_rot) hipLaunchKernelGGL(ud::plb_loss_contact<2>, gp, blk, 0, st, c, ud::PlbPrimArg<2>{h->prim, rr}, x, prim_pos, soft_contact, h->lred);
     else if (h->gen) hipLaunchKernelGGL(ud::plb_loss_contact<1>, gp, blk, 0, st, c, ud::PlbPrimArg<1>{h->prim}, x, prim_pos, soft_contact, h->lred);
@@ -856,9 +1012,10 @@ static int plb_loss_common(ud_plb* h, int B, const double* x, const double* prim
 }
 
 static int plb_loss_fwd_impl(const char* who, ud_plb* h, int B, const double* x, const double* prim_pos, const double* prim_rot, const double* target_density,
-                             const double* target_sdf, const double* weights, int soft_contact, double* loss, double* parts, void* stream) {
+                             const double* target_sdf, const double* weights, int soft_contact, double* loss, double* parts, void* stream,
+                             const double* prim_gap = nullptr) {
   hipStream_t st = (hipStream_t)stream;
-  int rc = plb_loss_common(h, B, x, prim_pos, prim_rot, target_density, target_sdf, weights, soft_contact, st);
+  int rc = plb_loss_common(h, B, x, prim_pos, prim_rot, target_density, target_sdf, weights, soft_contact, st, prim_gap);
   if (rc) return rc;
   hipLaunchKernelGGL(ud::plb_loss_finish, dim3((B + 63) / 64), dim3(64), 0, st, h->c, B, soft_contact, weights, (const double*)h->lred, loss, parts);
   hipError_t e = hipGetLastError();
@@ -868,16 +1025,21 @@ static int plb_loss_fwd_impl(const char* who, ud_plb* h, int B, const double* x,
 
 static int plb_loss_bwd_impl(const char* who, ud_plb* h, int B, const double* x, const double* prim_pos, const double* prim_rot, const double* target_density,
                              const double* target_sdf, const double* weights, int soft_contact, const double* g_loss, double* g_x, double* g_prim_pos,
-                             double* g_prim_rot, void* stream) {
+                             double* g_prim_rot, void* stream, const double* prim_gap = nullptr, double* g_prim_gap = nullptr) {
   hipStream_t st = (hipStream_t)stream;
-  int rc = plb_loss_common(h, B, x, prim_pos, prim_rot, target_density, target_sdf, weights, soft_contact, st);   // recompute the grid mass and the sums
+  int rc = plb_loss_common(h, B, x, prim_pos, prim_rot, target_density, target_sdf, weights, soft_contact, st, prim_gap);   // recompute the grid mass and the sums
   if (rc) return rc;
   if (g_prim_pos) { if (hipMemsetAsync(g_prim_pos, 0, (size_t)B * h->c.np * 3 * 8, st) != hipSuccess) { ud::set_error("%s: memset failed", who); return UD_ERR_HIP; } }
   if (g_prim_rot) { if (hipMemsetAsync(g_prim_rot, 0, (size_t)B * h->c.np * 4 * 8, st) != hipSuccess) { ud::set_error("%s: memset failed", who); return UD_ERR_HIP; } }
+  if (g_prim_gap) { if (hipMemsetAsync(g_prim_gap, 0, (size_t)B * h->c.np * 8, st) != hipSuccess) { ud::set_error("%s: memset failed", who); return UD_ERR_HIP; } }
   const dim3 blk(256), gp((h->c.N + 255) / 256, B);
   ud::PlbRot rr = h->rot;
   rr.rot = const_cast<double*>(prim_rot); rr.grot = g_prim_rot;
-  if (prim_rot && h->shape) hipLaunchKernelGGL(ud::plb_loss_bwd_kernel<4>, gp, blk, 0, st, h->c, ud::PlbPrimArg<4>{h->prim, rr, h->shp}, h->G, soft_contact, weights, x, prim_pos,
+  ud::PlbGap gg = h->gap;
+  gg.gap = const_cast<double*>(prim_gap); gg.ggap = g_prim_gap;
+  if (prim_gap) hipLaunchKernelGGL(ud::plb_loss_bwd_kernel<5>, gp, blk, 0, st, h->c, ud::PlbPrimArg<5>{h->prim, rr, h->shp, gg}, h->G, soft_contact, weights, x, prim_pos,
+                                   target_density, target_sdf, (const double*)h->gm, (const double*)h->lred, g_loss, g_x, g_prim_pos);
+  else if (prim_rot && h->shape) hipLaunchKernelGGL(ud::plb_loss_bwd_kernel<4>, gp, blk, 0, st, h->c, ud::PlbPrimArg<4>{h->prim, rr, h->shp}, h->G, soft_contact, weights, x, prim_pos,
                                                target_density, target_sdf, (const double*)h->gm, (const double*)h->lred, g_loss, g_x, g_prim_pos);
   else if (h->shape) hipLaunchKernelGGL(ud::plb_loss_bwd_kernel<3>, gp, blk, 0, st, h->c, ud::PlbPrimArg<3>{h->prim, h->shp}, h->G, soft_contact, weights, x, prim_pos,
                                         target_density, target_sdf, (const double*)h->gm, (const double*)h->lred, g_loss, g_x, g_prim_pos);
@@ -905,6 +1067,7 @@ int ud_plb_loss_fwd_rot(ud_plb* h, int B, const double* x, const double* prim_po
                         const double* weights, int soft_contact, double* loss, double* parts, void* stream) {
   if (!h || !x || !prim_pos || !prim_rot || !target_density || !target_sdf || !weights || !loss) { ud::set_error("ud_plb_loss_fwd_rot: null argument"); return UD_ERR_INVALID; }
   if (!h->rot_state) { ud::set_error("ud_plb_loss_fwd_rot: the handle was not created with rot_state (use ud_plb_loss_fwd)"); return UD_ERR_INVALID; }
+  if (h->chop) { ud::set_error("ud_plb_loss_fwd_rot: a Chopsticks handle (prim_kind[0] = 6) takes its distance at the current gap: use ud_plb_loss_fwd_gap"); return UD_ERR_INVALID; }
   return plb_loss_fwd_impl("ud_plb_loss_fwd_rot", h, B, x, prim_pos, prim_rot, target_density, target_sdf, weights, soft_contact, loss, parts, stream);
 }
 
@@ -919,7 +1082,24 @@ int ud_plb_loss_bwd_rot(ud_plb* h, int B, const double* x, const double* prim_po
                         const double* weights, int soft_contact, const double* g_loss, double* g_x, double* g_prim_pos, double* g_prim_rot, void* stream) {
   if (!h || !x || !prim_pos || !prim_rot || !target_density || !target_sdf || !weights || !g_loss || !g_x) { ud::set_error("ud_plb_loss_bwd_rot: null argument"); return UD_ERR_INVALID; }
   if (!h->rot_state) { ud::set_error("ud_plb_loss_bwd_rot: the handle was not created with rot_state (use ud_plb_loss_bwd)"); return UD_ERR_INVALID; }
+  if (h->chop) { ud::set_error("ud_plb_loss_bwd_rot: a Chopsticks handle (prim_kind[0] = 6) takes its distance at the current gap: use ud_plb_loss_bwd_gap"); return UD_ERR_INVALID; }
   return plb_loss_bwd_impl("ud_plb_loss_bwd_rot", h, B, x, prim_pos, prim_rot, target_density, target_sdf, weights, soft_contact, g_loss, g_x, g_prim_pos, g_prim_rot, stream);
+}
+
+int ud_plb_loss_fwd_gap(ud_plb* h, int B, const double* x, const double* prim_pos, const double* prim_rot, const double* prim_gap, const double* target_density,
+                        const double* target_sdf, const double* weights, int soft_contact, double* loss, double* parts, void* stream) {
+  if (!h || !x || !prim_pos || !prim_rot || !prim_gap || !target_density || !target_sdf || !weights || !loss) { ud::set_error("ud_plb_loss_fwd_gap: null argument"); return UD_ERR_INVALID; }
+  if (!h->chop) { ud::set_error("ud_plb_loss_fwd_gap: the handle has no Chopsticks (prim_kind[0] = 6): use ud_plb_loss_fwd%s", h->rot_state ? "_rot" : ""); return UD_ERR_INVALID; }
+  return plb_loss_fwd_impl("ud_plb_loss_fwd_gap", h, B, x, prim_pos, prim_rot, target_density, target_sdf, weights, soft_contact, loss, parts, stream, prim_gap);
+}
+
+int ud_plb_loss_bwd_gap(ud_plb* h, int B, const double* x, const double* prim_pos, const double* prim_rot, const double* prim_gap, const double* target_density,
+                        const double* target_sdf, const double* weights, int soft_contact, const double* g_loss, double* g_x, double* g_prim_pos, double* g_prim_rot,
+                        double* g_prim_gap, void* stream) {
+  if (!h || !x || !prim_pos || !prim_rot || !prim_gap || !target_density || !target_sdf || !weights || !g_loss || !g_x) { ud::set_error("ud_plb_loss_bwd_gap: null argument"); return UD_ERR_INVALID; }
+  if (!h->chop) { ud::set_error("ud_plb_loss_bwd_gap: the handle has no Chopsticks (prim_kind[0] = 6): use ud_plb_loss_bwd%s", h->rot_state ? "_rot" : ""); return UD_ERR_INVALID; }
+  return plb_loss_bwd_impl("ud_plb_loss_bwd_gap", h, B, x, prim_pos, prim_rot, target_density, target_sdf, weights, soft_contact, g_loss, g_x, g_prim_pos, g_prim_rot, stream,
+                           prim_gap, g_prim_gap);
 }
 
 }  // extern "C"

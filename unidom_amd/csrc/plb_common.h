@@ -165,10 +165,11 @@ struct PlbScale { double s[3]; };   // action scale of primitive 0 (set_velocity
 // of its own, and plb_grid_cell left to the letter: the persistent kernels inline that one at the edge of their register budget, and a
 // Sphere-only handle runs exactly the code it always ran.
 // ROT (a rot_state handle): Q0 = the quaternions of the env's primitives at substep f, Q0 + np*4 at f + 1.
-// SH (a shape handle): every kind but 0 collides so, through the shape layer; sh = the handle's shape constants.
-template <bool ROT = false, bool SH = false>
+// SH (a shape handle): every kind but 0 collides so, through the shape layer; sh = the handle's shape constants (SH == 2, a Chopsticks
+// handle: gap = the env's gaps [np] at substep f as well).
+template <bool ROT = false, int SH = 0>
 __device__ __forceinline__ void plb_grid_cell_gen(const PlbConst& c, const PlbPrim& pr, long lin, double m, const double* mv, const double* P0, const double* soft,
-                                                  double* vv, const double* Q0 = nullptr, const PlbShape* sh = nullptr) {
+                                                  double* vv, const double* Q0 = nullptr, const PlbShape* sh = nullptr, const double* gap = nullptr) {
   vv[0] = 0.0; vv[1] = 0.0; vv[2] = 0.0;
   if (!(m > 1e-12)) return;
   const int n = c.n_grid;
@@ -179,6 +180,8 @@ __device__ __forceinline__ void plb_grid_cell_gen(const PlbConst& c, const PlbPr
   const double* P1 = P0 + c.np * 3;
   for (int pi = 0; pi < c.np; ++pi) {
     if (plb_general<SH>(pr.kind[pi])) {
+      if constexpr (SH == 2) plb_collide_rot<2>(pr, pi, c.radius[pi], c.dt, gp, P0 + pi * 3, P1 + pi * 3, Q0 + pi * 4, Q0 + (c.np + pi) * 4, soft[pi], vv, sh, gap);
+      else
       if constexpr (ROT) plb_collide_rot<SH>(pr, pi, c.radius[pi], c.dt, gp, P0 + pi * 3, P1 + pi * 3, Q0 + pi * 4, Q0 + (c.np + pi) * 4, soft[pi], vv, sh);
       else plb_collide<SH>(pr, pi, c.radius[pi], c.dt, gp, P0 + pi * 3, P1 + pi * 3, soft[pi], vv, sh);
       continue;
@@ -208,11 +211,13 @@ __device__ __forceinline__ void plb_grid_cell_gen(const PlbConst& c, const PlbPr
   }
 }
 template <int GEN>   // 0: sticky Spheres only, 1: a general primitive, 2: a rot_state handle (Q0: the substep's quaternions, see plb_grid_cell_gen);
-                     // 3 / 4: a shape handle (Box, Cylinder, Torus) with constant orientation / on rot_state
+                     // 3 / 4: a shape handle (Box, Cylinder, Torus) with constant orientation / on rot_state; 5: a Chopsticks handle (rot_state;
+                     // gapf: the env's gaps at substep f)
 __device__ __forceinline__ void plb_grid_cell_any(const PlbConst& c, const PlbPrimArg<GEN>& pr, long lin, double m, const double* mv, const double* P0,
-                                                  const double* soft, double* vv, const double* Q0 = nullptr) {
-  if constexpr (GEN == 4) plb_grid_cell_gen<true, true>(c, pr.p, lin, m, mv, P0, soft, vv, Q0, &pr.s);
-  else if constexpr (GEN == 3) plb_grid_cell_gen<false, true>(c, pr.p, lin, m, mv, P0, soft, vv, nullptr, &pr.s);
+                                                  const double* soft, double* vv, const double* Q0 = nullptr, const double* gapf = nullptr) {
+  if constexpr (GEN == 5) plb_grid_cell_gen<true, 2>(c, pr.p, lin, m, mv, P0, soft, vv, Q0, &pr.s, gapf);
+  else if constexpr (GEN == 4) plb_grid_cell_gen<true, 1>(c, pr.p, lin, m, mv, P0, soft, vv, Q0, &pr.s);
+  else if constexpr (GEN == 3) plb_grid_cell_gen<false, 1>(c, pr.p, lin, m, mv, P0, soft, vv, nullptr, &pr.s);
   else if constexpr (GEN == 2) plb_grid_cell_gen<true>(c, pr.p, lin, m, mv, P0, soft, vv, Q0);
   else if constexpr (GEN == 1) plb_grid_cell_gen(c, pr.p, lin, m, mv, P0, soft, vv);
   else plb_grid_cell(c, lin, m, mv, P0, soft, vv);
@@ -252,12 +257,14 @@ struct ud_plb {
   ud::PlbScale ascale{{1.0, 1.0, 1.0}};
   bool rot_state = false;   // every primitive's orientation is per-env state (the _rot entry points); rot: its arenas and kinematics
   ud::PlbRot rot{};
+  bool chop = false;        // primitive 0 is a Chopsticks (the _gap entry points): the GEN = 5 kernels; gap: its arenas and constants
+  ud::PlbGap gap{};
   PlbCluster cl;
 };
 // every arena of the handle, once, at create (no allocation and no host synchronisation in any step call)
 int plb_reserve(ud_plb* h, int B, bool multi_kernel);
-struct PlbCkOff { size_t hist, pos, perm, gck_cnt, gck_lin, gck_val, svd, total, rot; };
-PlbCkOff plb_ckpt_layout(const ud::PlbConst& c, int B, bool rot = false);
+struct PlbCkOff { size_t hist, pos, perm, gck_cnt, gck_lin, gck_val, svd, total, rot, gap; };
+PlbCkOff plb_ckpt_layout(const ud::PlbConst& c, int B, bool rot = false, bool gap = false);
 void plb_bind_ckpt(ud::PlbArgs& a, const ud::PlbConst& c, int B, void* ckpt);
 // persistent path (plb_cluster.hip)
 int plb_cluster_plan(ud_plb* h, int max_envs);

@@ -306,11 +306,12 @@ __device__ __forceinline__ void plb_grid_cell_adj(const PlbConst& c, long lin, d
 // ---- the same for a handle with a general primitive (plb_prim.h; a function of its own for the reason given at plb_grid_cell_gen).  A cell sends
 // two independent vectors per primitive: q1[pi] adds to gpos[f + 1][pi], q0[pi] adds to gpos[f][pi] (a sticky sphere sends q0 = -q1).
 // ROT (a rot_state handle): Q0 as in plb_grid_cell_gen; gr0[pi] / gr1[pi] = what the cell sends to the cotangents of rotation[f] / rotation[f + 1].
-// SH (a shape handle): as in plb_grid_cell_gen.
-template <bool ROT = false, bool SH = false>
+// SH (a shape handle): as in plb_grid_cell_gen; SH == 2: gap likewise, gg[pi] = what the cell sends to the cotangent of gap[f][pi] (0 unless pi is a Chopsticks).
+template <bool ROT = false, int SH = 0>
 __device__ __forceinline__ void plb_grid_cell_adj_gen(const PlbConst& c, const PlbPrim& pr, long lin, double m, const double* mv, const double* gin, const double* P0,
                                                       const double* soft, double* ga, double q0[2][3], double q1[2][3], double& gfric,
-                                                      const double* Q0 = nullptr, double (*gr0)[4] = nullptr, double (*gr1)[4] = nullptr, const PlbShape* sh = nullptr) {
+                                                      const double* Q0 = nullptr, double (*gr0)[4] = nullptr, double (*gr1)[4] = nullptr, const PlbShape* sh = nullptr,
+                                                      double* gg = nullptr, const double* gap = nullptr) {
   ga[0] = 0; ga[1] = 0; ga[2] = 0; ga[3] = 0;
   if (!(m > 1e-12)) return;
   double g[3] = {gin[0], gin[1], gin[2]};
@@ -328,6 +329,8 @@ __device__ __forceinline__ void plb_grid_cell_adj_gen(const PlbConst& c, const P
 #pragma unroll
     for (int k = 0; k < 3; ++k) uin[pi][k] = vv[k];
     if (plb_general<SH>(pr.kind[pi])) {
+      if constexpr (SH == 2) stick[pi] = plb_collide_rot<2>(pr, pi, c.radius[pi], c.dt, gp, P0 + pi * 3, P1 + pi * 3, Q0 + pi * 4, Q0 + (c.np + pi) * 4, soft[pi], vv, sh, gap);
+      else
       if constexpr (ROT) stick[pi] = plb_collide_rot<SH>(pr, pi, c.radius[pi], c.dt, gp, P0 + pi * 3, P1 + pi * 3, Q0 + pi * 4, Q0 + (c.np + pi) * 4, soft[pi], vv, sh);
       else stick[pi] = plb_collide<SH>(pr, pi, c.radius[pi], c.dt, gp, P0 + pi * 3, P1 + pi * 3, soft[pi], vv, sh);
       continue;
@@ -393,6 +396,10 @@ __device__ __forceinline__ void plb_grid_cell_adj_gen(const PlbConst& c, const P
     if (plb_general<SH>(pr.kind[pi])) {      // the forward of this primitive again from the velocity that entered it, then in reverse
       PlbCollide k;
       double gu[3];
+      if constexpr (SH == 2) {
+        plb_collide_eval_rot<2>(pr, pi, c.radius[pi], c.dt, gp, P0 + pi * 3, P1 + pi * 3, Q0 + pi * 4, Q0 + (c.np + pi) * 4, soft[pi], uin[pi], k, sh, gap);
+        plb_collide_adj_rot<2>(pr, pi, c.dt, k, soft[pi], gp, P0 + pi * 3, Q0 + pi * 4, Q0 + (c.np + pi) * 4, g, gu, q0[pi], q1[pi], gr0[pi], gr1[pi], sh, gg + pi, gap);
+      } else
       if constexpr (ROT) {
         plb_collide_eval_rot<SH>(pr, pi, c.radius[pi], c.dt, gp, P0 + pi * 3, P1 + pi * 3, Q0 + pi * 4, Q0 + (c.np + pi) * 4, soft[pi], uin[pi], k, sh);
         plb_collide_adj_rot<SH>(pr, pi, c.dt, k, soft[pi], gp, P0 + pi * 3, Q0 + pi * 4, Q0 + (c.np + pi) * 4, g, gu, q0[pi], q1[pi], gr0[pi], gr1[pi], sh);

@@ -27,8 +27,8 @@ struct PlbRot {
   double* rot;      // [B][S+1][np][4] (w, x, y, z): handle arena, or the caller's checkpoint; the loss kernels: the caller's prim_rot [B][np][4]
   double* grot;     // [B][S+1][np][4] cotangent (adjoint only); the loss adjoint: the caller's g_prim_rot [B][np][4] (may be null)
   double* ext;      // the caller's [B][np][4] array of this launch: prim_rot (pack), prim_rot_out (unpack), g_prim_rot (adjoint pack; may be null)
-  int kin;          // kinematics of primitive 0: 1 = Primitive.forward_kinematics, 2 = RollingPin's
-  int adim;         // action dimensions: 3 or 6
+  int kin;          // kinematics of primitive 0: 1 = Primitive.forward_kinematics, 2 = RollingPin's, 3 = Chopsticks' (plb_gap_step, plb_qstep_right below)
+  int adim;         // action dimensions: 3 or 6 (7 on a Chopsticks handle)
   double sw[3];     // action.scale[3:6]
 };
 template <int GEN> struct PlbPrimArg {};
@@ -41,9 +41,27 @@ template <> struct PlbPrimArg<2> { PlbPrim p; PlbRot r; };
 struct PlbShape { double c[2][3]; };
 template <> struct PlbPrimArg<3> { PlbPrim p; PlbShape s; };
 template <> struct PlbPrimArg<4> { PlbPrim p; PlbRot r; PlbShape s; };
-// which kinds take Primitive.collide: the Capsule alone in the instantiations of before, every kind but the sticky Sphere on a shape handle
-template <bool SH> __device__ __forceinline__ bool plb_general(int kind) {
-  if constexpr (SH) return kind != 0; else return kind == 1;
+// A handle with a Chopsticks (PlbPrim.kind 6, primitive 0 only, always on rot_state; GEN = 5): the one kind whose shape is state.  Its opening
+// `gap` changes once per substep, so the trajectory of this step and its cotangent sit beside the rotation's.  The shape layer takes the gap
+// of the substep where the other kinds take their constants: a pointer to it stands in for PlbShape.c[pi] (plb_shape_consts).
+struct PlbGap {
+  double* gap;      // [B][S+1][np]: handle arena, or the caller's checkpoint; the loss kernels: the caller's prim_gap [B][np]
+  double* ggap;     // [B][S+1][np] cotangent (adjoint only); the loss adjoint: the caller's g_prim_gap [B][np] (may be null)
+  double* ext;      // the caller's [B][np] array of this launch: prim_gap (pack), g_prim_gap (adjoint pack; may be null)
+  double* ext_out;  // the forward pack: prim_gap_out [B][np]
+  double mingap[2]; // minimal_gap
+  double sg;        // action.scale[6]
+};
+template <> struct PlbPrimArg<5> { PlbPrim p; PlbRot r; PlbShape s; PlbGap g; };
+// which kinds take Primitive.collide: the Capsule alone in the instantiations of before, every kind but the sticky Sphere on a shape handle.
+// SH is 0 (no shape layer), 1 (Box, Cylinder, Torus, Capsule) or 2 (a Chopsticks handle: kind 6 as well; gap = the env's gaps [np] of the substep)
+template <int SH> __device__ __forceinline__ bool plb_general(int kind) {
+  if constexpr (SH != 0) return kind != 0; else return kind == 1;
+}
+// the constants the shape layer reads for primitive pi: the handle's, or for a Chopsticks its gap of this substep
+template <int SH> __device__ __forceinline__ const double* plb_shape_consts(const PlbPrim& pr, const PlbShape& sh, int pi, const double* gap) {
+  if constexpr (SH == 2) { if (pr.kind[pi] == 6) return gap + pi; }
+  return sh.c[pi];
 }
 // the extra argument of the pack / unpack kernels: nothing, or the above
 template <bool ROT> struct PlbRotArg {};
@@ -138,6 +156,17 @@ __device__ __forceinline__ void plb_qinv_adj(const double* q, const double* qi, 
 #pragma unroll
   for (int k = 1; k < 4; ++k) gq[k] -= (gqi[k] - dot * qi[k]) / n;
 }
+// Chopsticks.forward_kinematics (primitives.py:113-117) beside the base class's: the rotation step multiplies on the RIGHT, rot[f+1] =
+// qmul(rot[f], w2quat(w)) (a turn about the body's own axes; the base class has w2quat(w) on the left), and the opening closes against a floor,
+// gap[f+1] = max(gap[f] - gap_vel, minimal_gap).  Adjoints: gq / gdq / ggap / ggv are ADDED to; the arm of max is held constant -- the cotangent
+// passes where gap - gap_vel > minimal_gap and is zero where it is smaller; at exact equality it is unspecified (here: zero).
+__device__ __forceinline__ void plb_qstep_right(const double* q, const double* dq, double* q1) { plb_qmul(q, dq, q1); }
+__device__ __forceinline__ void plb_qstep_right_adj(const double* q, const double* dq, const double* gq1, double* gq, double* gdq) { plb_qmul_adj(q, dq, gq1, gq, gdq); }
+__device__ __forceinline__ double plb_gap_step(double gap, double gv, double mingap) { return fmax(gap - gv, mingap); }
+__device__ __forceinline__ void plb_gap_step_adj(double gap, double gv, double mingap, double g1, double& ggap, double& ggv) {
+  if (gap - gv > mingap) { ggap += g1; ggv -= g1; }
+}
+
 // the orientation a ROT = false instantiation reads (the handle's constant) or a ROT = true one is given
 template <bool ROT> __device__ __forceinline__ const double* plb_sel(const double* of_handle, const double* given) {
   if constexpr (ROT) return given; else return of_handle;
@@ -190,8 +219,32 @@ __device__ __forceinline__ double plb_box_sdf(const double* sz, const double* y,
   }
   return len + fmin(mx, 0.0);
 }
+// Chopsticks._sdf / _normal (primitives.py:130-147): two Capsules of the primitive's (h, r) side by side.  With p = pl + (0, h/2, 0) and delta =
+// (gap/2, 0, 0) stick a is the Capsule's _sdf at p - delta, stick b at p + delta, and that _sdf shifts y by h/2 AGAIN before it takes off
+// clamp(y, 0, h): both axis segments span local y in [-h, 0], at x = -+gap/2 -- the primitive's position is the sticks' top end, as the reference
+// has it.  sdf = min(a, b); the normal is stick a's where a <= b (a tie takes a for both), else stick b's.  Both sticks are evaluated here, once,
+// for the distance, the normal and the adjoint: p = the selected stick's vector from its axis segment (the sticks differ in p[0] alone), len =
+// length(p), pass_y as in plb_capsule_local, half = d p[0] / d gap (-1/2 for stick a, +1/2 for stick b).  The selection is a constant of the adjoint.
+__device__ __forceinline__ double plb_chop_pick(double gap, double ch, const double* pl, double* p, double& pass_y, double& half) {
+  const double py = (pl[1] + ch / 2) + ch / 2;
+  p[1] = py - fmin(fmax(py, 0.0), ch); p[2] = pl[2];
+  pass_y = (py >= 0.0 && py <= ch) ? 0.0 : 1.0;
+  const double xa = pl[0] - gap / 2, xb = pl[0] + gap / 2;
+  const double rest = p[1] * p[1] + p[2] * p[2] + 1e-14;
+  const double la = sqrt(xa * xa + rest), lb = sqrt(xb * xb + rest);
+  const bool a = la <= lb;                                   // a - r <= b - r
+  p[0] = a ? xa : xb; half = a ? -0.5 : 0.5;
+  return a ? la : lb;
+}
 // the distance alone (all a cell outside the shell, and the contact loss, need)
+template <int SH = 1>
 __device__ __forceinline__ double plb_shape_sdf(int kind, const double* sc, double ch, double radius, const double* pl) {
+  if constexpr (SH == 2) {
+    if (kind == 6) {                                         // Chopsticks: sc[0] = the gap of this substep (plb_shape_consts)
+      double p[3], pass_y, half;
+      return plb_chop_pick(sc[0], ch, pl, p, pass_y, half) - radius;
+    }
+  }
   if (kind == 3) return plb_box_sdf(sc, pl);
   if (kind == 4) {                                           // Cylinder: sc = (h, r), h the radial half extent and r the axial one
     const double l = sqrt(pl[0] * pl[0] + pl[2] * pl[2] + 1e-14);
@@ -219,7 +272,16 @@ __device__ __forceinline__ void plb_normalize3_adj(const double* n, const double
   for (int k = 0; k < 3; ++k) gn[k] = go[k] * il - s * n[k];
 }
 // the local normal (_normal of the kind)
+template <int SH = 1>
 __device__ __forceinline__ void plb_shape_normal(int kind, const double* sc, double ch, const double* pl, double* nl) {
+  if constexpr (SH == 2) {
+    if (kind == 6) {                                         // Chopsticks: the selected stick's p / len
+      double p[3], pass_y, half;
+      const double il = 1.0 / plb_chop_pick(sc[0], ch, pl, p, pass_y, half);
+      nl[0] = p[0] * il; nl[1] = p[1] * il; nl[2] = p[2] * il;
+      return;
+    }
+  }
   if (kind == 3) {                                           // Box: central differences of _sdf, normalised (:259-269)
     double n[3];
 #pragma unroll
@@ -251,8 +313,24 @@ __device__ __forceinline__ void plb_shape_normal(int kind, const double* sc, dou
     nl[0] = pl[0] * il; nl[1] = p1 * il; nl[2] = pl[2] * il;
   }
 }
-// cotangents (gdist of the distance, gnl of the local normal) -> cotangent of pl (assigned); the intermediates are formed again from pl
-__device__ __forceinline__ void plb_shape_adj(int kind, const double* sc, double ch, const double* pl, double gdist, const double* gnl, double* g) {
+// cotangents (gdist of the distance, gnl of the local normal) -> cotangent of pl (assigned); the intermediates are formed again from pl.
+// SH == 2: also ggap (assigned), the cotangent of the gap -- that of the selected stick's local point in x times -+1/2; 0 for every other kind
+template <int SH = 1>
+__device__ __forceinline__ void plb_shape_adj(int kind, const double* sc, double ch, const double* pl, double gdist, const double* gnl, double* g,
+                                              double* ggap = nullptr) {
+  if constexpr (SH == 2) {
+    *ggap = 0.0;
+    if (kind == 6) {                                         // Chopsticks: the Capsule's adjoint at the selected stick
+      double p[3], pass_y, half;
+      const double il = 1.0 / plb_chop_pick(sc[0], ch, pl, p, pass_y, half);
+      const double gl = gdist - (gnl[0] * p[0] + gnl[1] * p[1] + gnl[2] * p[2]) * il * il;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) g[k] = gnl[k] * il + gl * p[k] * il;
+      g[1] *= pass_y;
+      *ggap = half * g[0];
+      return;
+    }
+  }
   if (kind == 3) {
     double n[3], dg[3][3], gn[3], gs[3];
 #pragma unroll
@@ -321,17 +399,20 @@ __device__ __forceinline__ void plb_shape_adj(int kind, const double* sc, double
   }
 }
 // the pair the contact goes through on a shape handle, behind inv_trans as plb_capsule_local / _adj are: d = point - position -> pl and the distance
-template <bool ROT = false>
-__device__ __forceinline__ double plb_shape_local(const PlbPrim& pr, const PlbShape& sh, int pi, double radius, const double* d, double* pl, const double* qi = nullptr) {
+template <bool ROT = false, int SH = 1>
+__device__ __forceinline__ double plb_shape_local(const PlbPrim& pr, const PlbShape& sh, int pi, double radius, const double* d, double* pl, const double* qi = nullptr,
+                                                  const double* gap = nullptr) {
   plb_qrot(plb_sel<ROT>(pr.qi[pi], qi), d, pl);
-  return plb_shape_sdf(pr.kind[pi], sh.c[pi], pr.h[pi], radius, pl);
+  return plb_shape_sdf<SH>(pr.kind[pi], plb_shape_consts<SH>(pr, sh, pi, gap), pr.h[pi], radius, pl);
 }
-// cotangents (gdist, gnl, gpl of pl directly) -> cotangent of d; ROT: also gpl_all, the whole cotangent of pl
-template <bool ROT = false>
+// cotangents (gdist, gnl, gpl of pl directly) -> cotangent of d; ROT: also gpl_all, the whole cotangent of pl; SH == 2: also ggap (plb_shape_adj)
+template <bool ROT = false, int SH = 1>
 __device__ __forceinline__ void plb_shape_local_adj(const PlbPrim& pr, const PlbShape& sh, int pi, const double* pl, double gdist, const double* gnl, const double* gpl,
-                                                    double* gd, const double* qi = nullptr, double* gpl_all = nullptr) {
+                                                    double* gd, const double* qi = nullptr, double* gpl_all = nullptr, double* ggap = nullptr,
+                                                    const double* gap = nullptr) {
   double g[3];
-  plb_shape_adj(pr.kind[pi], sh.c[pi], pr.h[pi], pl, gdist, gnl, g);
+  if constexpr (SH == 2) plb_shape_adj<2>(pr.kind[pi], plb_shape_consts<2>(pr, sh, pi, gap), pr.h[pi], pl, gdist, gnl, g, ggap);
+  else plb_shape_adj(pr.kind[pi], sh.c[pi], pr.h[pi], pl, gdist, gnl, g);
 #pragma unroll
   for (int k = 0; k < 3; ++k) g[k] += gpl[k];
   plb_qrot_t(plb_sel<ROT>(pr.qi[pi], qi), g, gd);
@@ -346,20 +427,20 @@ struct PlbCollide {
 };
 // what p holds differs by handle: the Capsule's unnormalised vector from the axis segment (with len and pass_y beside it), and on a shape handle
 // (SH) the unit local normal itself, len and pass_y unused.  Read the unit local normal through this, never through p directly.
-template <bool SH> __device__ __forceinline__ void plb_local_normal(const PlbCollide& k, double* nl) {
-  if constexpr (SH) { nl[0] = k.p[0]; nl[1] = k.p[1]; nl[2] = k.p[2]; }
+template <int SH> __device__ __forceinline__ void plb_local_normal(const PlbCollide& k, double* nl) {
+  if constexpr (SH != 0) { nl[0] = k.p[0]; nl[1] = k.p[1]; nl[2] = k.p[2]; }
   else { nl[0] = k.p[0] / k.len; nl[1] = k.p[1] / k.len; nl[2] = k.p[2] / k.len; }
 }
 // gp: cell position, P0 / P1: the primitive's position at substeps f / f + 1, sf: softness, u: the cell velocity so far; ROT: q0 / qi / q1 =
 // rotation[f], conj / |.| of it, rotation[f + 1]
-// SH (a shape handle): distance and normal through the shape layer, sh = the handle's shape constants
-template <bool ROT = false, bool SH = false>
+// SH (a shape handle): distance and normal through the shape layer, sh = the handle's shape constants (SH == 2: with the gap of this substep)
+template <bool ROT = false, int SH = 0>
 __device__ __forceinline__ void plb_collide_eval(const PlbPrim& pr, int pi, double radius, double dt, const double* gp, const double* P0, const double* P1,
                                                  double sf, const double* u, PlbCollide& k, const double* q0 = nullptr, const double* qi = nullptr,
-                                                 const double* q1 = nullptr, const PlbShape* sh = nullptr) {
+                                                 const double* q1 = nullptr, const PlbShape* sh = nullptr, const double* gap = nullptr) {
   const double d[3] = {gp[0] - P0[0], gp[1] - P0[1], gp[2] - P0[2]};
-  if constexpr (SH) {
-    k.dist = plb_shape_local<ROT>(pr, *sh, pi, radius, d, k.pl, qi);
+  if constexpr (SH != 0) {
+    k.dist = plb_shape_local<ROT, SH>(pr, *sh, pi, radius, d, k.pl, qi, gap);
   } else {
     k.len = plb_capsule_local<ROT>(pr, pi, d, k.pl, k.p, k.pass_y, qi);
     k.dist = k.len - radius;
@@ -369,7 +450,7 @@ __device__ __forceinline__ void plb_collide_eval(const PlbPrim& pr, int pi, doub
   k.active = (sf > 0 && k.infl > 0.1) || k.dist <= 0;       // no 0.001 and no trailing `and softness > 0`: those are the Sphere override's
   k.flag = false;
   if (!k.active) return;
-  if constexpr (SH) plb_shape_normal(pr.kind[pi], sh->c[pi], pr.h[pi], k.pl, k.p);
+  if constexpr (SH != 0) plb_shape_normal<SH>(pr.kind[pi], plb_shape_consts<SH>(pr, *sh, pi, gap), pr.h[pi], k.pl, k.p);
   double nl[3], back[3];
   plb_local_normal<SH>(k, nl);
   plb_qrot(plb_sel<ROT>(pr.q[pi], q0), nl, k.D);
@@ -389,7 +470,7 @@ __device__ __forceinline__ void plb_collide_eval(const PlbPrim& pr, int pi, doub
   for (int i = 0; i < 3; ++i) k.ts[i] = k.flag ? k.t[i] / k.tn * s : k.t[i];
 }
 // u <- collide(u); returns whether the primitive acted on the cell
-template <bool SH = false>
+template <int SH = 0>
 __device__ __forceinline__ bool plb_collide(const PlbPrim& pr, int pi, double radius, double dt, const double* gp, const double* P0, const double* P1, double sf,
                                             double* u, const PlbShape* sh = nullptr) {
   PlbCollide k;
@@ -400,18 +481,19 @@ __device__ __forceinline__ bool plb_collide(const PlbPrim& pr, int pi, double ra
   return true;
 }
 // the same on a rot_state handle: q0 / q1 = rotation[f] / rotation[f + 1] of this env and primitive
-template <bool SH = false>
+template <int SH = 0>
 __device__ __forceinline__ void plb_collide_eval_rot(const PlbPrim& pr, int pi, double radius, double dt, const double* gp, const double* P0, const double* P1,
-                                                     const double* q0, const double* q1, double sf, const double* u, PlbCollide& k, const PlbShape* sh = nullptr) {
+                                                     const double* q0, const double* q1, double sf, const double* u, PlbCollide& k, const PlbShape* sh = nullptr,
+                                                     const double* gap = nullptr) {
   double qi[4];
   plb_qinv(q0, qi);
-  plb_collide_eval<true, SH>(pr, pi, radius, dt, gp, P0, P1, sf, u, k, q0, qi, q1, sh);
+  plb_collide_eval<true, SH>(pr, pi, radius, dt, gp, P0, P1, sf, u, k, q0, qi, q1, sh, gap);
 }
-template <bool SH = false>
+template <int SH = 0>
 __device__ __forceinline__ bool plb_collide_rot(const PlbPrim& pr, int pi, double radius, double dt, const double* gp, const double* P0, const double* P1,
-                                                const double* q0, const double* q1, double sf, double* u, const PlbShape* sh = nullptr) {
+                                                const double* q0, const double* q1, double sf, double* u, const PlbShape* sh = nullptr, const double* gap = nullptr) {
   PlbCollide k;
-  plb_collide_eval_rot<SH>(pr, pi, radius, dt, gp, P0, P1, q0, q1, sf, u, k, sh);
+  plb_collide_eval_rot<SH>(pr, pi, radius, dt, gp, P0, P1, q0, q1, sf, u, k, sh, gap);
   if (!k.active) return false;
 #pragma unroll
   for (int i = 0; i < 3; ++i) u[i] = k.cv[i] + k.w[i] * (1 - k.infl) + k.ts[i] * k.infl;
@@ -420,10 +502,11 @@ __device__ __forceinline__ bool plb_collide_rot(const PlbPrim& pr, int pi, doubl
 // adjoint of an ACTIVE collide: G = cotangent of u_out (in), cotangent of u_in (out, may alias nothing of the inputs); g0 / g1 = cotangents of P_f / P_{f+1}.
 // ROT: also gq0 / gq1 = cotangents of rotation[f] (through the normal's rotation back, the local point and the inverse with its normalisation) and of
 // rotation[f + 1] (through the collider velocity), assigned; d = cell - P_f.
-template <bool ROT = false, bool SH = false>
+template <bool ROT = false, int SH = 0>   // SH == 2: gap as plb_collide_eval took it; also ggap (assigned), the cotangent of gap[pi]
 __device__ __forceinline__ void plb_collide_adj(const PlbPrim& pr, int pi, double dt, const PlbCollide& k, double sf, const double* G, double* gu, double* g0,
                                                 double* g1, const double* q0 = nullptr, const double* qi = nullptr, const double* q1 = nullptr,
-                                                const double* d = nullptr, double* gq0 = nullptr, double* gq1 = nullptr, const PlbShape* sh = nullptr) {
+                                                const double* d = nullptr, double* gq0 = nullptr, double* gq1 = nullptr, const PlbShape* sh = nullptr,
+                                                double* ggap = nullptr, const double* gap = nullptr) {
   double gcv[3], gw[3], gt[3], gD[3];
   double ginfl = 0, gnc = 0;
 #pragma unroll
@@ -459,7 +542,8 @@ __device__ __forceinline__ void plb_collide_adj(const PlbPrim& pr, int pi, doubl
   plb_qrot_t(plb_sel<ROT>(pr.q[pi], q1), gback, gpl);
   plb_qrot_t(plb_sel<ROT>(pr.q[pi], q0), gD, gnl);
   [[maybe_unused]] double gpl_all[3];
-  if constexpr (SH) plb_shape_local_adj<ROT>(pr, *sh, pi, k.pl, glen, gnl, gpl, gd, qi, gpl_all);
+  if constexpr (SH == 2) plb_shape_local_adj<ROT, 2>(pr, *sh, pi, k.pl, glen, gnl, gpl, gd, qi, gpl_all, ggap, gap);
+  else if constexpr (SH != 0) plb_shape_local_adj<ROT>(pr, *sh, pi, k.pl, glen, gnl, gpl, gd, qi, gpl_all);
   else plb_capsule_local_adj<ROT>(pr, pi, k.p, k.len, k.pass_y, glen, gnl, gpl, gd, qi, gpl_all);
 #pragma unroll
   for (int i = 0; i < 3; ++i) g0[i] = -gd[i];                // d = g - P_f
@@ -472,14 +556,14 @@ __device__ __forceinline__ void plb_collide_adj(const PlbPrim& pr, int pi, doubl
     plb_qinv_adj(q0, qi, gqi, gq0);
   }
 }
-template <bool SH = false>
+template <int SH = 0>
 __device__ __forceinline__ void plb_collide_adj_rot(const PlbPrim& pr, int pi, double dt, const PlbCollide& k, double sf, const double* gp, const double* P0,
                                                     const double* q0, const double* q1, const double* G, double* gu, double* g0, double* g1, double* gq0,
-                                                    double* gq1, const PlbShape* sh = nullptr) {
+                                                    double* gq1, const PlbShape* sh = nullptr, double* ggap = nullptr, const double* gap = nullptr) {
   double qi[4];
   plb_qinv(q0, qi);
   const double d[3] = {gp[0] - P0[0], gp[1] - P0[1], gp[2] - P0[2]};
-  plb_collide_adj<true, SH>(pr, pi, dt, k, sf, G, gu, g0, g1, q0, qi, q1, d, gq0, gq1, sh);
+  plb_collide_adj<true, SH>(pr, pi, dt, k, sf, G, gu, g0, g1, q0, qi, q1, d, gq0, gq1, sh, ggap, gap);
 }
 
 }  // namespace ud

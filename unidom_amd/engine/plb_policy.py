@@ -78,6 +78,9 @@ class PlbPolicy:
     def __init__(self, sim, hidden_dims=(256, 256), activation="relu", n_observed_particles=200, shared=False):
         if activation not in ACTIVATIONS:
             raise ValueError(f"activation {activation!r}: one of {sorted(ACTIVATIONS)}")
+        if getattr(sim, "chopsticks", False):       # the reference's MLP asserts the same (engine/nn/mlp.py:26-27): its observation has no gap
+            raise ValueError("PlbPolicy: a Chopsticks simulator (prim_kind[0] = 6) is not supported: the observation carries seven numbers per "
+                             "primitive and the gap is not among them")
         self.sim, self.activation, self.shared = sim, activation, bool(shared)
         self.n_observed_particles = int(n_observed_particles)
         self.obs_step, self.obs_num, self.dims = policy_dims(sim.n_particles, sim.n_primitive, sim.action_dim, hidden_dims,

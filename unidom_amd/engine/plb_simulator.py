@@ -33,6 +33,7 @@ class PlbState(NamedTuple):
     nu: torch.Tensor         # [B]
     yield_stress: torch.Tensor  # [B]
     prim_rot: Optional[torch.Tensor] = None   # [B,n_prim,4] (w, x, y, z): a rot_state simulator only
+    prim_gap: Optional[torch.Tensor] = None   # [B,n_prim]: a Chopsticks simulator only (the opening of primitive 0; primitive 1's entry is carried along)
 
 
 class PlbConf:
@@ -70,6 +71,12 @@ class PlbConf:
     rot_state = False
     action_dim = 3
     action_scale_w = (1.0, 1.0, 1.0)
+    # prim_kind 6 = Chopsticks (primitive 0 only; needs rot_state and action_dim 7 = (v, w, gap_vel)): two Capsules of (prim_h, prim_radius) whose
+    # opening is state (PlbState.prim_gap, reset to prim_init_gap) and closes once per substep by gap_vel = clip(action[6]) * action_scale_gap /
+    # substeps, never below prim_min_gap
+    prim_min_gap = (0.0, 0.0)
+    prim_init_gap = (0.0, 0.0)
+    action_scale_gap = 1.0
     softness = 666.0         # Primitive cfg default, set_softness()
     # True: the handle is created with the unit action scale and `step` applies action.clamp(-1, 1) * action_scale in torch (the kernel's own
     # clip is then the identity; torch's clamp passes the cotangent at equality, as the header specifies) -- a Sphere handle with a scale
@@ -118,6 +125,36 @@ class WriterConf(PlbConf):
     prim_rot = ((0.0, 0.0, 0.0, 1.0),)
     prim_friction = (0.0,)
     action_scale = (0.01, 0.01, 0.01)
+    lower_bound = (0.0, 0.05, 0.0)
+    upper_bound = (1.0, 1.0, 1.0)
+
+
+class ChopsticksConf(PlbConf):
+    """A small Chopsticks task.  THIS PROJECT'S OWN CHOICE: the reference registers a `Chopsticks` env name (plb/envs/__init__.py:6) but ships no
+    chopsticks.yml, so there is no file to mirror.  The primitive takes the reference's defaults (primitives.py:166-173: h 0.06, r 0.03,
+    minimal_gap 0.06, init_gap 0.06); the body is a 600-particle block on the floor, the sticks hang over it with their top end (the
+    primitive's position) at y = 0.2 and open to 0.1, and the seven action dimensions are scaled as the Writer's.  Runs the multi-kernel path."""
+    n_particles = 600
+    E = 5e3
+    nu = 0.35
+    yield_stress = 50.0
+    gravity = (0.0, -1.0, 0.0)
+    ground_friction = 100.0
+    box_width = (0.1, 0.1, 0.1)
+    box_init_pos = (0.5, 0.05, 0.5)
+    prim_kind = (6,)
+    prim_radius = (0.03,)
+    prim_h = (0.06,)
+    prim_init_pos = ((0.5, 0.2, 0.5),)
+    prim_rot = ((1.0, 0.0, 0.0, 0.0),)
+    prim_friction = (0.9,)
+    prim_min_gap = (0.06,)
+    prim_init_gap = (0.1,)
+    rot_state = True
+    action_dim = 7
+    action_scale = (0.01, 0.01, 0.01)
+    action_scale_w = (0.05, 0.05, 0.05)
+    action_scale_gap = 0.01
     lower_bound = (0.0, 0.05, 0.0)
     upper_bound = (1.0, 1.0, 1.0)
 
@@ -213,6 +250,77 @@ class _PlbStepRot(torch.autograd.Function):
         sim._prof_end(ev)
         sim.ground_friction_grad = ofr if sim.ground_friction_grad is None else sim.ground_friction_grad + ofr
         return None, ox, ov, oC, oF, op, orot, None, oa, oE, onu, oys
+
+
+class _PlbStepGap(torch.autograd.Function):
+    """_PlbStepRot over ud_plb_step_fwd_gap / _bwd_gap: prim_gap [B,P] is a state tensor and a differentiable leaf as well, action [B,7]."""
+    @staticmethod
+    def forward(ctx, sim, x, v, Cm, F, pp, pr, pg, so, action, E, nu, ys):
+        L = _lib.lib()
+        B = x.shape[0]
+        x, v, Cm, F, pp, pr, pg, so, action, E, nu, ys = map(_c, (x, v, Cm, F, pp, pr, pg, so, action, E, nu, ys))
+        xo, vo, Co, Fo, po, ro, go = (torch.empty_like(t) for t in (x, v, Cm, F, pp, pr, pg))
+        ckpt = None
+        if any(ctx.needs_input_grad):
+            ckpt = torch.empty((L.ud_plb_ckpt_bytes(sim._h, C.c_int(B)) // 8,), dtype=torch.float64, device=x.device)
+        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        ev = sim._prof_begin("fwd")
+        _lib.check(L.ud_plb_step_fwd_gap(sim._h, C.c_int(B), _p(x), _p(v), _p(Cm), _p(F), _p(pp), _p(pr), _p(pg), _p(so), _p(action), _p(E), _p(nu),
+                                         _p(ys), _p(xo), _p(vo), _p(Co), _p(Fo), _p(po), _p(ro), _p(go), _p(ckpt), stream), "ud_plb_step_fwd_gap")
+        sim._prof_end(ev)
+        ctx.sim, ctx.B = sim, B
+        ctx.save_for_backward(ckpt, so, action, E, nu, ys)
+        return xo, vo, Co, Fo, po, ro, go
+
+    @staticmethod
+    def backward(ctx, gx, gv, gC, gF, gpp, gpr, gpg):
+        L = _lib.lib()
+        sim, B = ctx.sim, ctx.B
+        ckpt, so, action, E, nu, ys = ctx.saved_tensors
+        if ckpt is None:
+            raise _lib.UnidomError("PLB step backward without a checkpoint (forward ran under no_grad)")
+        N, P, dev = sim.n_particles, sim.n_primitive, so.device
+        g = lambda t: None if t is None else _c(t)
+        gx, gv, gC, gF, gpp, gpr, gpg = map(g, (gx, gv, gC, gF, gpp, gpr, gpg))
+        mk = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+        ox, ov, oC, oF, op, orot, ogap, oa = mk(B, N, 3), mk(B, N, 3), mk(B, N, 3, 3), mk(B, N, 3, 3), mk(B, P, 3), mk(B, P, 4), mk(B, P), mk(B, 7)
+        oE, onu, oys, ofr = mk(B), mk(B), mk(B), mk(B)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        ev = sim._prof_begin("bwd")
+        _lib.check(L.ud_plb_step_bwd_gap(sim._h, C.c_int(B), _p(ckpt), _p(so), _p(action), _p(E), _p(nu), _p(ys), _p(gx), _p(gv), _p(gC),
+                                         _p(gF), _p(gpp), _p(gpr), _p(gpg), _p(ox), _p(ov), _p(oC), _p(oF), _p(op), _p(orot), _p(ogap), _p(oa), _p(oE),
+                                         _p(onu), _p(oys), _p(ofr), stream), "ud_plb_step_bwd_gap")
+        sim._prof_end(ev)
+        sim.ground_friction_grad = ofr if sim.ground_friction_grad is None else sim.ground_friction_grad + ofr
+        return None, ox, ov, oC, oF, op, orot, ogap, None, oa, oE, onu, oys
+
+
+class _PlbLossGap(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, sim, x, pp, pr, pg, td, ts, wt, soft):
+        L = _lib.lib()
+        B = x.shape[0]
+        x, pp, pr, pg = _c(x), _c(pp), _c(pr), _c(pg)
+        loss = torch.empty((B,), dtype=torch.float64, device=x.device)
+        parts = torch.empty((B, 3), dtype=torch.float64, device=x.device)
+        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        _lib.check(L.ud_plb_loss_fwd_gap(sim._h, C.c_int(B), _p(x), _p(pp), _p(pr), _p(pg), _p(td), _p(ts), _p(wt), C.c_int(int(soft)), _p(loss),
+                                         _p(parts), stream), "ud_plb_loss_fwd_gap")
+        ctx.sim, ctx.B, ctx.soft = sim, B, soft
+        ctx.save_for_backward(x, pp, pr, pg, td, ts, wt)
+        ctx.mark_non_differentiable(parts)
+        return loss, parts
+
+    @staticmethod
+    def backward(ctx, gl, _gparts):
+        L = _lib.lib()
+        x, pp, pr, pg, td, ts, wt = ctx.saved_tensors
+        gl = _c(gl)
+        gx, gpp, gpr, gpg = torch.empty_like(x), torch.empty_like(pp), torch.empty_like(pr), torch.empty_like(pg)
+        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        _lib.check(L.ud_plb_loss_bwd_gap(ctx.sim._h, C.c_int(ctx.B), _p(x), _p(pp), _p(pr), _p(pg), _p(td), _p(ts), _p(wt), C.c_int(int(ctx.soft)),
+                                         _p(gl), _p(gx), _p(gpp), _p(gpr), _p(gpg), stream), "ud_plb_loss_bwd_gap")
+        return None, gx, gpp, gpr, gpg, None, None, None, None
 
 
 class _PlbLossRot(torch.autograd.Function):
@@ -337,6 +445,7 @@ class PlbSimulator:
         self.prim_kind = tuple(int(k) for k in pad(cfg.prim_kind, 0))[:P]
         self.rot_state = bool(getattr(cfg, "rot_state", False))
         self.action_dim = int(getattr(cfg, "action_dim", 3)) or 3
+        self.chopsticks = P > 0 and self.prim_kind[0] == 6          # the _gap entry points: PlbState.prim_gap is state
         rot = (C.c_double * 4 * 2)(*[(C.c_double * 4)(*q) for q in pad(cfg.prim_rot, (0.0, 0.0, 0.0, 0.0))])
         shape = (C.c_double * 3 * 2)(*[(C.c_double * 3)(*(list(sc) + [0.0] * 3)[:3]) for sc in pad(getattr(cfg, "prim_shape", ()), (0.0, 0.0, 0.0))])
         cc = _lib.ud_plb_conf(
@@ -348,7 +457,8 @@ class PlbSimulator:
             prim_kind=(C.c_int * 2)(*pad(cfg.prim_kind, 0)), capsule_h=(C.c_double * 2)(*pad(cfg.prim_h, 0.0)), prim_rot=rot,
             prim_friction=(C.c_double * 2)(*pad(cfg.prim_friction, 0.0)), action_scale=(C.c_double * 3)(*handle_scale),
             rot_state=int(self.rot_state), action_dim=int(getattr(cfg, "action_dim", 3)),
-            action_scale_w=(C.c_double * 3)(*getattr(cfg, "action_scale_w", (1.0, 1.0, 1.0))), prim_shape=shape)
+            action_scale_w=(C.c_double * 3)(*getattr(cfg, "action_scale_w", (1.0, 1.0, 1.0))), prim_shape=shape,
+            min_gap=(C.c_double * 2)(*pad(getattr(cfg, "prim_min_gap", ()), 0.0)), action_scale_gap=float(getattr(cfg, "action_scale_gap", 1.0)))
         self._h = C.c_void_p()
         self.profile = None    # {"fwd": [], "bwd": []}: HIP-event pairs around every step call, on its stream (bench.py)
         self.ground_friction_grad = None   # [B], accumulated by backward() (optimize_ground_friction.grad); reset it by hand
@@ -403,13 +513,19 @@ class PlbSimulator:
                         E=torch.full((B,), float(cfg.E), dtype=torch.float64, device=dev),
                         nu=torch.full((B,), float(cfg.nu), dtype=torch.float64, device=dev),
                         yield_stress=torch.full((B,), float(cfg.yield_stress), dtype=torch.float64, device=dev),
-                        prim_rot=rep(f64([tuple(q) for q in list(cfg.prim_rot)[:self.n_primitive]])) if self.rot_state else None)
+                        prim_rot=rep(f64([tuple(q) for q in list(cfg.prim_rot)[:self.n_primitive]])) if self.rot_state else None,
+                        prim_gap=rep(f64((list(getattr(cfg, "prim_init_gap", ())) + [0.0, 0.0])[:self.n_primitive])) if self.chopsticks else None)
 
     def step(self, state: PlbState, action) -> PlbState:
         """TaichiEnv.step(action) in copy mode: one call = `substeps` substeps for every env.  Differentiable: when any of
         the state tensors / the action / E / nu / yield_stress requires grad, the forward keeps a checkpoint and backward()
         runs the adjoint kernels (substep_grad)."""
         B = state.x.shape[0]
+        if self.chopsticks:     # action [B,7]; orientation and gap are stepped with the position
+            action = torch.as_tensor(action, dtype=torch.float64, device=self.device).reshape(B, 7)
+            xo, vo, Co, Fo, po, ro, go = _PlbStepGap.apply(self, state.x, state.v, state.C, state.F, state.prim_pos, state.prim_rot, state.prim_gap,
+                                                           state.softness, action, state.E, state.nu, state.yield_stress)
+            return state._replace(x=xo, v=vo, C=Co, F=Fo, prim_pos=po, prim_rot=ro, prim_gap=go)
         if self.rot_state:      # action [B,action_dim]; the orientation is stepped with the position
             action = torch.as_tensor(action, dtype=torch.float64, device=self.device).reshape(B, self.action_dim)
             xo, vo, Co, Fo, po, ro = _PlbStepRot.apply(self, state.x, state.v, state.C, state.F, state.prim_pos, state.prim_rot, state.softness,
@@ -429,6 +545,8 @@ class PlbSimulator:
         ts = torch.as_tensor(target_sdf, dtype=torch.float64, device=self.device).reshape(-1).contiguous()
         assert td.numel() == self.n_grid ** 3 == ts.numel()
         wt = torch.as_tensor(weights, dtype=torch.float64, device=self.device).reshape(3).contiguous()
+        if self.chopsticks:
+            return _PlbLossGap.apply(self, state.x, state.prim_pos, state.prim_rot, state.prim_gap, td, ts, wt, bool(soft_contact))
         if self.rot_state:
             return _PlbLossRot.apply(self, state.x, state.prim_pos, state.prim_rot, td, ts, wt, bool(soft_contact))
         return _PlbLoss.apply(self, state.x, state.prim_pos, td, ts, wt, bool(soft_contact))
