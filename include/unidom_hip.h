@@ -707,6 +707,110 @@ int ud_mpm_finish_bwd(int B, int N, int n_prim, int S, int Q, const float* x, co
                       const float* g_obs, float* g_x, float* g_v, float* g_C, float* g_F, float* const* g_prim_pos,
                       float* g_shift, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * PLB renderer: TaichiEnv.render() (GenORM/policy/pbm/plb/engine/renderer/renderer.py, renderer_utils.py) for B envs per call.
+ * A handle of its own; ud_plb_conf is not involved.  f32 throughout, as the reference's fields are.  The operation order written
+ * below IS the contract: tests/plb_render_twin.py restates it in NumPy f32 and is the specification.  Parity with the reference
+ * itself is UNPINNED by reference data: neither Taichi nor cv2 can be run beside this library, so no image of the reference's was
+ * ever compared; the order below is read off its source.  Every a*b+c below is a rounded multiply, then a rounded add; divisions
+ * and square roots are correctly rounded; norm(v) = sqrtf((v0*v0 + v1*v1) + v2*v2); normalize(v) = (1.0f / norm(v)) * v.
+ * Not covered (UD_ERR_UNSUPPORTED at create): use_directional_light, use_roulette.  The `target` overlay (commented out in the
+ * reference's next_hit) does not exist here.
+ *
+ * Arenas, all allocated at create for max_envs: 16 B per voxel cell and env (packed volume 8, sdf 4, smoothing scratch 4); the
+ * reference's separate colour volume (12 B) is not kept, the colour bytes are decoded from the packed volume when sampled.  The
+ * calls below launch (or enqueue copies) only: no allocation, no host synchronisation.
+ *
+ * ud_plb_render_bake (set_particles, :453-480, build_sdf_from_particles :88-131): x [B,N,3] f64, color [N] i32 (0xRRGGBB) ->
+ *   bbox [B,2,3], status [B]; volume and sdf stay in the handle.  Per env: px = (float)x; bbox0[c] = min_i (floorf(px[c] * inv_dx)
+ *   - 6.0f) * dx with dx = (float)conf.dx, inv_dx = (float)(1.0 / conf.dx); hi[c] the same with max; status = 1 when (hi[c] -
+ *   bbox0[c]) / dx >= voxel_res[c] on any axis (the reference's assert) -- such an env is not baked and every later output of it
+ *   is zero; bbox1 = (float)((double)bbox0 + voxel_res * (double)dx).  Every cell starts at 2^32 - 1.  For every particle and every
+ *   offset (i,j,k) in [-bake_size-1, bake_size]^3: p = (px - bbox0) * inv_dx; idx = (int)p + (i,j,k), skipped outside the volume;
+ *   d = (float)idx - p; dist = sqrtf((d0*d0 + d1*d1) + d2*d2); q = fminf(fmaxf(0, 51.0f * dist), 255.0f); atomic 64-bit min of
+ *   ((int64)q << 24) + color.  sdf = ((c >> 24) & 255) / 255.0f; colour channel j = ((c >> 8 (2 - j)) & 255) / 255.0f.  Two
+ *   smoothing passes (sdf -> scratch -> sdf): a boundary cell becomes 1, an interior one (sum of its 27 neighbours) / 27.0f, the
+ *   sum starting from 0.0f with the first axis's offset outermost and the last innermost.  Volumes are [rx][ry][rz], z fastest.
+ * ud_plb_render_read_volume: copies the packed volume [B,rx,ry,rz] (i64) and / or the smoothed sdf (f32) out (either may be NULL).
+ *
+ * Primitive state of the two calls below: prim_pos [B,n_prim,3], prim_rot [B,n_prim,4] (w,x,y,z; NULL = identity), prim_gap
+ *   [B,n_prim] (read for a Chopsticks only; NULL otherwise), f64.  Distance and normal of primitive i at the f32 point pp:
+ *   the shape layer of csrc/plb_prim.h in f64 (kinds 0..6) at qrot(conj(rot) / |rot|, (double)pp - pos), the normal turned back
+ *   by qrot(rot, .), both cast to f32.
+ *
+ * ud_plb_render_gbuffer: the first hit of one ray per pixel through the pixel centre (both jitters 0.5), outputs [B,res0,res1]
+ *   indexed (env, u, v): kind (0 nothing, 1 background plane, 2 ground, 3 + i primitive i, 16 body), t, normal [.,3], albedo [.,3].
+ *   Camera: mat = Ry(camera_rot[1]) @ Rx(camera_rot[0]) as at :433-441, formed in f64 at create and rounded to nine f32;
+ *   c = normalize(((0.46f * (u + ju)) / res1 - (float)(0.23 * res0 / res1)) - 1e-5f, ((0.46f * (v + jv)) / res1 - 0.23f) - 1e-5f,
+ *   -1); d[r] = (mat[r][0] * c0 + mat[r][1] * c1) + mat[r][2] * c2; o = camera_pos.
+ *   next_hit (:202-325) as written, closest = 1e10f, roughness = 0.05f at the start:
+ *     plane: d2 != 0: rc = -(o2 + 5.5f) / d2, taken when rc > 0 and rc < closest; normal (0,0,1), colour (0.6,0.7,0.7), roughness 0.
+ *     ground: d1 < 0: gd = (o1 + 0.002f) / (-d1), taken when gd < 100 and gd < closest; normal (0,1,0), roughness 0; p = o + d * gd;
+ *       colour (0.3,0.5,0.7) * f, f = (float)(((int)(p0 / 0.25f) + (int)(p2 / 0.25f)) % 2) * 0.2f + 0.35f inside [0,1]^2, else 0.4f.
+ *     primitives: dist = 0, sdf = 1e10f; while j < 200 and dist < 100 and sdf > 1e-8f: pp = o + dist * d; sdf = the smallest
+ *       distance (the first primitive on a tie); dist += sdf.  Taken when dist < closest and dist < 100; normal at o + dist * d.
+ *     body: ray_aabb_intersection (renderer_utils.py:42-70) with bbox; tnear = max(tnear, 0); pos = o + d * (tnear + 1e-4f);
+ *       500 steps: s = sample_sdf(pos); s < 0: back = step, 20 times { back = back * 0.5f; if sample_sdf(pos - back) < 0: pos =
+ *       pos - back }, dist = norm(o - pos), taken when dist < closest (normal, colour below; roughness keeps its value), stop;
+ *       else step = d * fmaxf(s * 0.05f, 0.01f), pos += step.
+ *     sample_sdf(pos): q = (pos - bbox0) / (bbox1 - bbox0); 0.0f unless every q[c] in [0,1]; else sample_tex(sdf, q) -
+ *       (float)sdf_threshold.  sample_tex: p = q * res; base = min((int)p, res - 1); f = p - base; base1 = min(base + 1, res - 1);
+ *       c00 = T[x,y,z] (1 - f0) + T[x1,y,z] f0; c01 = T[x,y,z1] .. T[x1,y,z1]; c10 = T[x,y1,z] .. T[x1,y1,z]; c11 = T[x,y1,z1] ..
+ *       T[x1,y1,z1]; c0 = c00 (1 - f1) + c10 f1; c1 = c01 (1 - f1) + c11 f1; c0 (1 - f2) + c1 f2.  Colour: the same per channel.
+ *     normal: n[i] = 500.0f * (sample_sdf(p + 1e-3f e_i) - sample_sdf(p - 1e-3f e_i)), normalized.
+ *
+ * ud_plb_render_image: render + trace + copy (:346-451) for spp samples (0 = the conf's) -> img [B,res1,res0,3] f32, already in
+ *   render_frame's orientation (img[:, ::-1].transpose(1, 0, 2): row = res1 - 1 - v, column = u).  Per sample: the ray above with
+ *   jitters r(.,.,0), r(.,.,1); throughput 1; up to max_ray_depth times: hit = next_hit(pos, d); hp = pos + t * d; if norm(normal)
+ *   != 0: out_dir(normal) (renderer_utils.py:8-18: u = (1,0,0), or normalize(cross(n, (0,1,0))) when |n1| < 0.999f; v = cross(n, u);
+ *   phi = 6.2831855f * r_phi; ay = sqrtf(r_r); ax = sqrtf(1 - r_r); ax * (cosf(phi) * u + sinf(phi) * v) + ay * n), glossy =
+ *   (x, yz cosf(phi'), yz sinf(phi')) * roughness with x = r_u * 2 - 1, phi' = (r_v * 2) * 3.1415927f, yz = sqrtf(1 - x * x);
+ *   d = normalize(out_dir + glossy); pos = hp + 1e-4f * d; throughput *= colour; else stop.  hit_sky is never cleared in the
+ *   reference, so the sample is throughput * sky_color(d): c = clamp(((d0 * 0.8f + d1 * 0.65f) + d2 * 0.15f) * 0.5f + 0.5f, 0, 1),
+ *   (c * 0.9f + (1 - c) * (0.7f, 0.7f, 0.8f)) * 1.5f.  Samples are summed in order from 0.0f.  copy: darken = 1 - 0.9f *
+ *   fmaxf(sqrtf((u / res0 - 0.5f)^2 + (v / res1 - 0.5f)^2) - 0.0f, 0); img = sqrtf(((sum * darken) * 1.5f) / (float)spp).
+ *   cosf / sinf are the device library's (an ulp from any other).
+ *   The random draws are THIS PROJECT'S OWN (ti.random cannot be pinned): r(pixel, sample, k) = (h >> 8) * 2^-24, h =
+ *   lowbias32(seed ^ (pixel * 0x9E3779B9 + sample * 0x85EBCA6B + k * 0xC2B2AE35)) in u32 wrap-around arithmetic, pixel = u * res1
+ *   + v (the env does not enter: equal envs give equal images), lowbias32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *=
+ *   0x846ca68b; x ^= x >> 16.  k = 0, 1: the pixel jitters; bounce b: k = 2 + 4b + (0 phi, 1 r of out_dir; 2 u, 3 v of glossy).
+ *
+ * B < 1 or B > max_envs, a null handle or array (prim_pos on a handle with primitives; prim_gap with a Chopsticks): UD_ERR_INVALID,
+ * nothing launched, no output touched.  Results are bit-identical from run to run.
+ * ------------------------------------------------------------------------------------------------ */
+#define UD_PLB_RENDER_MAX_PRIM 4
+typedef struct ud_plb_render ud_plb_render;
+/* (a tagged struct: the generated binding stub of INTEGRATION.md lists the three simulator confs) */
+typedef struct ud_plb_render_conf {
+  double dx;                  /* cfg.RENDERER.dx, default 1 / 150 */
+  int voxel_res[3];           /* (168, 168, 168); each >= 2 * bake_size and in [2, 1024], else UD_ERR_INVALID */
+  int bake_size;              /* 6 */
+  double sdf_threshold;       /* 0.65 * 0.56 */
+  int image_res[2];           /* (512, 512) */
+  int spp;                    /* 50: what ud_plb_render_image takes for spp = 0 */
+  int max_ray_depth;          /* 2 */
+  double camera_pos[3];       /* (0.5, 1.2, 4.0) */
+  double camera_rot[2];       /* (0.2, 0.0) */
+  int use_directional_light;  /* must be 0 (UD_ERR_UNSUPPORTED) */
+  int use_roulette;           /* must be 0 (UD_ERR_UNSUPPORTED) */
+  int n_primitives;           /* 0 .. UD_PLB_RENDER_MAX_PRIM */
+  int prim_kind[UD_PLB_RENDER_MAX_PRIM];         /* as ud_plb_conf.prim_kind, 0 .. 6 */
+  double prim_radius[UD_PLB_RENDER_MAX_PRIM];    /* Sphere / Capsule / RollingPin / Chopsticks radius */
+  double prim_h[UD_PLB_RENDER_MAX_PRIM];         /* Capsule / RollingPin / Chopsticks height */
+  double prim_shape[UD_PLB_RENDER_MAX_PRIM][3];  /* as ud_plb_conf.prim_shape (Box, Cylinder, Torus) */
+  float prim_color[UD_PLB_RENDER_MAX_PRIM][3];   /* the primitive's cfg colour */
+  int n_particles;            /* N of every bake call */
+  int max_envs;               /* arenas are allocated for this many envs; a call with more returns UD_ERR_INVALID */
+} ud_plb_render_conf;
+int ud_plb_render_create(const ud_plb_render_conf* conf, ud_plb_render** out);
+int ud_plb_render_destroy(ud_plb_render* h);
+int ud_plb_render_bake(ud_plb_render* h, int B, const double* x, const int* color, float* bbox, int* status, void* stream);
+int ud_plb_render_read_volume(ud_plb_render* h, int B, long long* packed, float* sdf, void* stream);
+int ud_plb_render_gbuffer(ud_plb_render* h, int B, const double* prim_pos, const double* prim_rot, const double* prim_gap, int* kind,
+                          float* t, float* normal, float* albedo, void* stream);
+int ud_plb_render_image(ud_plb_render* h, int B, const double* prim_pos, const double* prim_rot, const double* prim_gap, int spp,
+                        unsigned int seed, float* img, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,7 @@ SYMBOLS = [
     "ud_plb_grid_mass", "ud_plb_target_work_bytes", "ud_plb_target_sdf", "ud_plb_density_iou_work_bytes", "ud_plb_density_iou",
     "ud_plb_density_seq_work_bytes", "ud_plb_density_seq_sign_bytes", "ud_plb_density_seq_fwd", "ud_plb_density_seq_bwd", "ud_plb_chamfer",
     "ud_plb_policy_n_params", "ud_plb_policy_tape_bytes", "ud_plb_policy_fwd", "ud_plb_policy_bwd",
+    "ud_plb_render_create", "ud_plb_render_destroy", "ud_plb_render_bake", "ud_plb_render_read_volume", "ud_plb_render_gbuffer", "ud_plb_render_image",
     "ud_pc_fps", "ud_pc_ball_query", "ud_pc_group_fwd", "ud_pc_group_bwd",
     "ud_chamfer_fwd", "ud_chamfer_bwd", "ud_cloth_pnp_fwd", "ud_cloth_pnp_bwd", "ud_cloth_depth_fwd", "ud_cloth_depth_bwd",
     "ud_mpm_focus_fwd", "ud_mpm_focus_bwd", "ud_mpm_finish_fwd", "ud_mpm_finish_bwd",
@@ -61,6 +62,18 @@ class ud_plb_conf(C.Structure):
                 ("prim_friction", C.c_double * 2), ("action_scale", C.c_double * 3),
                 ("rot_state", C.c_int), ("action_dim", C.c_int), ("action_scale_w", C.c_double * 3),
                 ("prim_shape", (C.c_double * 3) * 2), ("min_gap", C.c_double * 2), ("action_scale_gap", C.c_double)]
+
+
+RENDER_MAX_PRIM = 4   # UD_PLB_RENDER_MAX_PRIM
+
+
+class ud_plb_render_conf(C.Structure):
+    _fields_ = [("dx", C.c_double), ("voxel_res", C.c_int * 3), ("bake_size", C.c_int), ("sdf_threshold", C.c_double),
+                ("image_res", C.c_int * 2), ("spp", C.c_int), ("max_ray_depth", C.c_int), ("camera_pos", C.c_double * 3),
+                ("camera_rot", C.c_double * 2), ("use_directional_light", C.c_int), ("use_roulette", C.c_int), ("n_primitives", C.c_int),
+                ("prim_kind", C.c_int * RENDER_MAX_PRIM), ("prim_radius", C.c_double * RENDER_MAX_PRIM), ("prim_h", C.c_double * RENDER_MAX_PRIM),
+                ("prim_shape", (C.c_double * 3) * RENDER_MAX_PRIM), ("prim_color", (C.c_float * 3) * RENDER_MAX_PRIM),
+                ("n_particles", C.c_int), ("max_envs", C.c_int)]
 
 
 def build(force: bool = False) -> str:
@@ -119,6 +132,12 @@ def lib():
         shape = [C.c_int] * 6 + [C.c_void_p, C.c_int, C.c_double]     # B N P obs_step obs_num n_layer dims activation velocity_weight
         L.ud_plb_policy_fwd.argtypes = shape + [C.c_void_p] * 5 + [C.c_long] + [C.c_void_p] * 3
         L.ud_plb_policy_bwd.argtypes = shape + [C.c_void_p, C.c_long] + [C.c_void_p] * 8
+        L.ud_plb_render_create.argtypes = [C.c_void_p, C.c_void_p]
+        L.ud_plb_render_destroy.argtypes = [C.c_void_p]
+        L.ud_plb_render_bake.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
+        L.ud_plb_render_read_volume.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 3
+        L.ud_plb_render_gbuffer.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 8
+        L.ud_plb_render_image.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_uint] + [C.c_void_p] * 2
         L.ud_pc_fps.argtypes = [C.c_int] * 3 + [C.c_void_p] * 4
         L.ud_pc_ball_query.argtypes = [C.c_int] * 3 + [C.c_float, C.c_int] + [C.c_void_p] * 5
         L.ud_pc_group_fwd.argtypes = [C.c_int] * 5 + [C.c_void_p] * 6

@@ -36,6 +36,7 @@ constexpr int PCL_H = 1024, PCL_LOGH = 10;      // >= PCL_PP * 27 = 864 cells a 
 constexpr int PCL_REC = PCL_PP * 27;            // cell records per part and substep (checkpoint)
 constexpr int PCL_SMAX = 128;                   // substeps per step call the primitive trajectory in LDS is sized for
 constexpr int PCL_BAR_STRIDE = 64, PCL_BAR_GEN = 32, PCL_BAR_EXIT = 48;
+constexpr int PCL_XCDS = 8;                     // XCDs workgroup ids are dealt over round-robin: the 8 of pcl_decode / pcl_grid (MI355X)
 constexpr unsigned PCL_SPIN = 1u << 22;         // polls (~1 us each) before a part gives up
 
 // Diagnostic build only (-DUD_PCL_STAMPS, tools/pcl_stamps.sh): s_memtime at the phase boundaries of the two kernels, summed over thread 0
@@ -763,6 +764,11 @@ int plb_cluster_plan(ud_plb* h, int max_envs) {
   (void)hipGetLastError();
   const int occ = std::min(occ_f, occ_b);
   if (occ < 1 || n_cu < 8) return 0;
+  // pcl_decode puts all W parts of an env on workgroup ids congruent mod 8: under round-robin placement they share ONE XCD, which holds
+  // (n_cu / PCL_XCDS) * occ workgroups.  An env with more parts than that can never be resident at once -- its first parts would wait for siblings
+  // that cannot start (N > 1024 at occupancy 1 on 256 CUs: the 1500-particle sheets of RopeConf / TableConf).  Such a handle runs the
+  // multi-kernel path.
+  if ((long)cl.W > (long)(n_cu / ud::PCL_XCDS) * occ) return 0;
   int per = (int)(((long)n_cu * occ) / cl.W);
   if (per >= 8) per = per / 8 * 8;                              // whole XCD rounds (speed only)
   const size_t budget = (size_t)24 << 30;                        // bytes of exchange grids a handle may hold

@@ -107,6 +107,56 @@ class MoveConf(PlbConf):
     action_scale_on_host = True
 
 
+class RopeConf(PlbConf):
+    """GenORM/policy/pbm/plb/envs/rope.yml over plb/config/default_config.py, the paper's "unfold cloth" task: a 1500-particle sheet
+    0.4 x 0.01 x 0.4 hanging over one Sphere that lifts and drops it.  The scale is applied on the host, so a handle of up to 1024 particles runs
+    the persistent path; at the file's 1500 an env has more parts than one XCD holds and the library picks the multi-kernel path (launch_plan() == 1)."""
+    n_particles = 1500                        # SHAPES[0].n_particles
+    E = 5e3                                   # default_config.py (the file sets neither E nor nu)
+    nu = 0.35                                 # default_config.py
+    yield_stress = 50.0                       # default_config.py:15 (rope.yml does not set it; table.yml, move.yml and torus.yml set 1762.2)
+    gravity = (0.0, -0.4, 0.0)                # SIMULATOR.gravity
+    ground_friction = 0.5                     # SIMULATOR.ground_friction
+    box_width = (0.4, 0.01, 0.4)              # SHAPES[0].width
+    box_init_pos = (0.5, 0.04, 0.5)           # SHAPES[0].init_pos
+    particle_color = 100                      # SHAPES[0].color: the key is given twice, ((0<<8) + (150<<16) + 150) then 100; the second wins: blue
+    prim_kind = (0,)                          # PRIMITIVES[0].shape: Sphere
+    prim_radius = (0.025,)                    # PRIMITIVES[0].radius
+    prim_h = (0.0,)                           # (a Sphere has none)
+    prim_init_pos = ((0.5, 0.05, 0.5),)       # PRIMITIVES[0].init_pos
+    prim_rot = ((1.0, 0.0, 0.0, 0.0),)        # Primitive default init_rot
+    prim_friction = (0.0,)                    # (read by no Sphere kernel: the Sphere is sticky)
+    prim_color = ((0.7, 0.7, 0.7),)           # PRIMITIVES[0].color
+    action_scale = (0.005, 0.005, 0.005)      # PRIMITIVES[0].action.scale
+    action_scale_on_host = True               # the Sphere kernels (see PlbConf)
+    # RENDERER: the top-down camera the experts of solve_action are selected through (use_directional_light is commented out: the default, off)
+    render_overrides = {"camera_pos": (0.5, 2.0, 0.5), "camera_rot": (1.57, 0.0)}
+
+
+class TableConf(PlbConf):
+    """GenORM/policy/pbm/plb/envs/table.yml over plb/config/default_config.py, the paper's "lift cloth" task: the same sheet lying on the floor,
+    one Sphere beside its corner.  The scale is applied on the host; which path runs: see RopeConf."""
+    n_particles = 1500                        # SHAPES[0].n_particles
+    E = 5e3                                   # default_config.py
+    nu = 0.35                                 # default_config.py
+    yield_stress = 1762.2                     # SIMULATOR.yield_stress
+    gravity = (0.0, -0.4, 0.0)                # SIMULATOR.gravity
+    ground_friction = 0.5                     # SIMULATOR.ground_friction
+    box_width = (0.4, 0.01, 0.4)              # SHAPES[0].width
+    box_init_pos = (0.5, 0.01, 0.5)           # SHAPES[0].init_pos
+    particle_color = 100                      # SHAPES[0].color
+    prim_kind = (0,)                          # PRIMITIVES[0].shape: Sphere
+    prim_radius = (0.035,)                    # PRIMITIVES[0].radius
+    prim_h = (0.0,)                           # (a Sphere has none)
+    prim_init_pos = ((0.65, 0.025, 0.35),)    # PRIMITIVES[0].init_pos
+    prim_rot = ((1.0, 0.0, 0.0, 0.0),)        # Primitive default init_rot
+    prim_friction = (0.0,)                    # (read by no Sphere kernel)
+    prim_color = ((0.7, 0.7, 0.7),)           # PRIMITIVES[0].color
+    action_scale = (0.005, 0.005, 0.005)      # PRIMITIVES[0].action.scale
+    action_scale_on_host = True               # the Sphere kernels (see PlbConf)
+    render_overrides = {"use_directional_light": False}   # RENDERER.use_directional_light: False (the default camera)
+
+
 class WriterConf(PlbConf):
     """PlasticineLab/sim2sim/plb/envs/writer.yml over sim2sim/plb/config/default_config.py: a 10 000-particle box on the floor
     (ground_friction 100: the floor stops what touches it) and one frictionless Capsule.  Runs the multi-kernel path."""
@@ -605,6 +655,16 @@ class PlbSimulator:
         if return_mins:
             return out.reshape(lead), mab.reshape(lead + (Na,)), mba.reshape(lead + (Nb,))
         return out.reshape(lead)
+
+    def render(self, state: PlbState, spp=None, seed=0, mode="rgb_array", render_conf=None, color=None, strict=True):
+        """TaichiEnv.render (taichi_env.py:88-94) of every env of `state`: engine/plb_render.py's PlbRenderer, created on the first call from
+        the conf's RENDERER overrides (or `render_conf`) and kept.  uint8 [B,H,W,3] ("rgb_array") or the f32 image ("float"); color and strict
+        as PlbRenderer.render takes them.  Passing a `render_conf` OBJECT other than the one the kept renderer was made from (compared by
+        identity, not by value) frees that renderer's arenas and creates a new one: keep one RenderConf and pass it every time, or none."""
+        from .plb_render import PlbRenderer
+        if getattr(self, "_renderer", None) is None or (render_conf is not None and render_conf is not self._renderer.conf):
+            self._renderer = PlbRenderer(self.cfg, render_conf, self.batch_size, self.device)
+        return self._renderer.render(state, spp=spp, seed=seed, mode=mode, color=color, strict=strict)
 
     @staticmethod
     def set_softness1(state: PlbState, softness) -> PlbState:   # primitives.py: Primitives.set_softness1
