@@ -16,6 +16,14 @@
 
 namespace ud {
 
+// clip_grad_lt(x, 0, 1) from the sign of p = x (1 - x): two compares instead of four.  p > 0 exactly for 0 < x < 1 (1 - x >= 2^-24 there
+// and the product of a positive float with it is positive, denormals kept); p = +-0 exactly on either bound (x = -0 included);
+// p < 0 outside, -inf for +-inf, NaN for NaN: 1 / 0.5 / 0 as clip_grad_lt gives them.
+__device__ __forceinline__ float clip_grad_01(float x) {
+  const float p = x * (1.f - x);
+  return p > 0.f ? 1.0f : (p == 0.f ? 0.5f : 0.0f);
+}
+
 __device__ __forceinline__ f2 fma2(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
 // a0 b0 + a1 b1 + a2 b2 as  fma(a2, b2, fma(a0, b0, a1 b1)):  the middle product is the one that is rounded
 __device__ __forceinline__ float dot3_m(float a0, float a1, float a2, float b0, float b1, float b2) {
@@ -71,14 +79,15 @@ constexpr int UD_CLOTH_MAXP = 1024 + 1;   // LDS plane stride (floats; the kerne
 // NORM = ClothBwdArgs::normalize as a compile-time switch: between barrier 1 and barrier 2 the substep is one basic block (no
 // branch on `normalize`, and the primitive cotangent's pieces run in every wave -- it is zero outside lanes 0-7 of wave 0 and stays
 // zero), so the scheduler can start the position reads of force_pairs_x under the norm chain.
-template <bool NORM>
+// FULL = the body fills its waves (P == Pp, fold_cloth1's 512 particles): no padding lane, so `live` is a constant and its selects go.
+template <bool NORM, bool FULL>
 __device__ __forceinline__ void cloth_rollout_bwd_fast(const ClothBwdArgs& a, float* ldsf) {
   // ldsf: Xs[3][MAXP] | Gs[3][MAXP] | red[2][16][UD_RSTR] | mac[16*8]
   const ClothConst c = a.c;
   const int i = threadIdx.x, b = blockIdx.x;
   const int P = c.P, Pp = c.Pp, S = c.S, B = a.B, T = a.T;
   const int nw = Pp >> 6, lane = i & 63, wv = i >> 6;
-  const bool live = i < P;
+  const bool live = FULL || i < P;
   // single-buffered: every X read sits between barrier 1 and barrier 2 and the next X write comes after barrier 2;
   // every G read sits between barrier 2 and the next barrier 1 and the next G write comes after that barrier
   float* Xs = ldsf;
@@ -171,7 +180,7 @@ __device__ __forceinline__ void cloth_rollout_bwd_fast(const ClothBwdArgs& a, fl
       float av[3], bv[3], bx[3];
 #pragma unroll
       for (int d = 0; d < 3; ++d) {
-        const float Dx = clip_grad_lt(x2[d], 0.f, 1.f);
+        const float Dx = clip_grad_01(x2[d]);
         const float Dv = (fabsf(vnext[d]) < c.max_v) ? 1.f : 0.f;
         av[d] = Dx * gx[d]; bv[d] = Dv * gv[d]; bx[d] = Dv * gx[d];
       }
@@ -231,7 +240,7 @@ __device__ __forceinline__ void cloth_rollout_bwd_fast(const ClothBwdArgs& a, fl
       force_pairs_x<UD_CLOTH_MAXP>(c, nbs, Xs, k, iL2, mu, x, v, v3, &in);
       if (LOSE) wp.drop();
 #pragma unroll
-      for (int d = 0; d < 3; ++d) v4[d] = m0 ? act[3] * v3[d] : v3[d];
+      for (int d = 0; d < 3; ++d) v4[d] = v3[d] * (m0 ? act[3] : 1.f);   // the suction as a factor (sc0 of the gripper-0 block below): x * 1 = x bit for bit
       // ---- reverse: clip (:326-329) and the two grippers (:313-314) with their normalisations folded in ----
       float gx2n[3], gv5n[3];
 #pragma unroll
@@ -259,7 +268,7 @@ __device__ __forceinline__ void cloth_rollout_bwd_fast(const ClothBwdArgs& a, fl
         for (int d = 0; d < 3; ++d) { ga[d] = __builtin_fmaf(h0, gxd[d], ga[d]); gv3[d] *= sc0; }
       }
       // primitives (:322-323), uniform; counted once (lane 0) in the action accumulators
-      gpl *= clip_grad_lt(psl + addl, 0.f, 1.f);
+      gpl *= clip_grad_01(psl + addl);
       gaP += pm3 ? gpl : 0.f;
       // ---- v3 = (v1 + F dt) damp ; ground friction (:281-290) ----
       float gF[3];
@@ -354,20 +363,33 @@ __device__ __forceinline__ void cloth_rollout_bwd_fast(const ClothBwdArgs& a, fl
   }
 }
 
-__global__ void __launch_bounds__(512) cloth_rollout_bwd_fast_kernel(ClothBwdArgs a) {   // normalised cotangents: the training default
+// One kernel per variant under a plain name (profiles and counter passes are keyed by kernel name).  The training default -- normalised
+// cotangents, a body that fills its waves -- keeps the name it always had; `_ragged` = a body with padding lanes in its last wave.
+__global__ void __launch_bounds__(512) cloth_rollout_bwd_fast_ragged_kernel(ClothBwdArgs a) {
   extern __shared__ float ldsf[];
-  cloth_rollout_bwd_fast<true>(a, ldsf);
+  cloth_rollout_bwd_fast<true, false>(a, ldsf);
+}
+
+__global__ void __launch_bounds__(512) cloth_rollout_bwd_fast_ragged_raw_kernel(ClothBwdArgs a) {
+  extern __shared__ float ldsf[];
+  cloth_rollout_bwd_fast<false, false>(a, ldsf);
+}
+
+__global__ void __launch_bounds__(512) cloth_rollout_bwd_fast_kernel(ClothBwdArgs a) {
+  extern __shared__ float ldsf[];
+  cloth_rollout_bwd_fast<true, true>(a, ldsf);
 }
 
 __global__ void __launch_bounds__(512) cloth_rollout_bwd_fast_raw_kernel(ClothBwdArgs a) {
   extern __shared__ float ldsf[];
-  cloth_rollout_bwd_fast<false>(a, ldsf);
+  cloth_rollout_bwd_fast<false, true>(a, ldsf);
 }
 
 void cloth_launch_bwd_fast(const ClothBwdArgs& a, hipStream_t stream) {
   const size_t shmem = (size_t)(6 * UD_CLOTH_MAXP + 2 * 16 * UD_RSTR + 16 * 8) * sizeof(float);
-  if (a.normalize) hipLaunchKernelGGL(cloth_rollout_bwd_fast_kernel, dim3(a.B), dim3(a.c.Pp), shmem, stream, a);
-  else hipLaunchKernelGGL(cloth_rollout_bwd_fast_raw_kernel, dim3(a.B), dim3(a.c.Pp), shmem, stream, a);
+  auto* kern = a.c.P == a.c.Pp ? (a.normalize ? cloth_rollout_bwd_fast_kernel : cloth_rollout_bwd_fast_raw_kernel)
+                               : (a.normalize ? cloth_rollout_bwd_fast_ragged_kernel : cloth_rollout_bwd_fast_ragged_raw_kernel);
+  hipLaunchKernelGGL(kern, dim3(a.B), dim3(a.c.Pp), shmem, stream, a);
 }
 
 }  // namespace ud
