@@ -714,8 +714,9 @@ int ud_mpm_finish_bwd(int B, int N, int n_prim, int S, int Q, const float* x, co
  * itself is UNPINNED by reference data: neither Taichi nor cv2 can be run beside this library, so no image of the reference's was
  * ever compared; the order below is read off its source.  Every a*b+c below is a rounded multiply, then a rounded add; divisions
  * and square roots are correctly rounded; norm(v) = sqrtf((v0*v0 + v1*v1) + v2*v2); normalize(v) = (1.0f / norm(v)) * v.
- * Not covered (UD_ERR_UNSUPPORTED at create): use_directional_light, use_roulette.  The `target` overlay (commented out in the
- * reference's next_hit) does not exist here.
+ * The directional light and Russian roulette (envs/torus.yml sets use_directional_light) are handle state, set by
+ * ud_plb_render_set_light below; the two conf fields of those names must stay 0 (UD_ERR_UNSUPPORTED at create).  The `target`
+ * overlay (commented out in the reference's next_hit) does not exist here.
  *
  * Arenas, all allocated at create for max_envs: 16 B per voxel cell and env (packed volume 8, sdf 4, smoothing scratch 4); the
  * reference's separate colour volume (12 B) is not kept, the colour bytes are decoded from the packed volume when sampled.  The
@@ -773,7 +774,27 @@ int ud_mpm_finish_bwd(int B, int N, int n_prim, int S, int Q, const float* x, co
  *   The random draws are THIS PROJECT'S OWN (ti.random cannot be pinned): r(pixel, sample, k) = (h >> 8) * 2^-24, h =
  *   lowbias32(seed ^ (pixel * 0x9E3779B9 + sample * 0x85EBCA6B + k * 0xC2B2AE35)) in u32 wrap-around arithmetic, pixel = u * res1
  *   + v (the env does not enter: equal envs give equal images), lowbias32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *=
- *   0x846ca68b; x ^= x >> 16.  k = 0, 1: the pixel jitters; bounce b: k = 2 + 4b + (0 phi, 1 r of out_dir; 2 u, 3 v of glossy).
+ *   0x846ca68b; x ^= x >> 16.  k = 0, 1: the pixel jitters; bounce b: k = 2 + 4b + (0 phi, 1 r of out_dir; 2 u, 3 v of glossy);
+ *   k = 2^30 + 4b + (0, 1, 2 the light noise; 3 the roulette) -- the two ranges stay apart up to bounce 2^28 - 2.
+ *
+ * ud_plb_render_set_light: use_directional_light / use_roulette of cfg.RENDERER (:374-397) as handle state; host only (no launch,
+ *   no allocation), read by the next ud_plb_render_image (ud_plb_render_gbuffer is unaffected).  light_direction is rounded to
+ *   f32 at the call.  A null argument, a direction that is not finite in f32, or an all-zero one with use_directional_light on:
+ *   UD_ERR_INVALID, the handle unchanged.  With both flags 0 the handle is a fresh one's (the image is bit-identical).  The image
+ *   kernel is compiled once per (light, roulette); what the two add to the loop above:
+ *   light, after pos = hp + 1e-4f * d and throughput *= colour of bounce b: noise[j] = (r_j - 0.5f) * 0.03f; direct =
+ *     normalize(light_direction + noise); dot = (direct0 * n0 + direct1 * n1) + direct2 * n2; if dot > 0 and next_hit(pos, direct)
+ *     returns a distance > 100: contrib += (throughput * 1.0f) * dot (light_color is 1); contrib starts at 0 per sample.  The
+ *     sample is then contrib and the sky term is NOT added (:408-410).  The shadow ray is answered by an any-hit search: next_hit's
+ *     candidates in next_hit's order with next_hit's conditions, stopping at the first one <= 100, no normal or colour fetched --
+ *     next_hit's closest is its smallest candidate, so this is the same boolean.  The background plane z = -5.5 takes part: a
+ *     light_direction with negative z meets it at -(pos2 + 5.5f) / direct2, which is <= 100 wherever pos2 <= 100 |direct2| - 5.5
+ *     (for (2, 1, -0.7): z <= 24.4, about 20 away from anything in view).  Such a light is therefore occluded at every first hit
+ *     of a camera that looks along -z (those lie at z <= camera z) and a max_ray_depth 1 image is exactly zero; with more bounces
+ *     only a ray that lands on the unbounded ground that far behind the camera is lit.  The reference's behaviour as written; kept.
+ *   roulette, at the end of every loop iteration, the one that hit the sky included: max_c = fmaxf(fmaxf(t0, t1), t2) of the
+ *     throughput; if r > max_c: stop, throughput = 0; else throughput[c] = throughput[c] / max_c.  max_c == 0 with r == 0 divides
+ *     0 by 0 as the reference does (NaN throughput from there on); kept as written.
  *
  * B < 1 or B > max_envs, a null handle or array (prim_pos on a handle with primitives; prim_gap with a Chopsticks): UD_ERR_INVALID,
  * nothing launched, no output touched.  Results are bit-identical from run to run.
@@ -791,8 +812,8 @@ typedef struct ud_plb_render_conf {
   int max_ray_depth;          /* 2 */
   double camera_pos[3];       /* (0.5, 1.2, 4.0) */
   double camera_rot[2];       /* (0.2, 0.0) */
-  int use_directional_light;  /* must be 0 (UD_ERR_UNSUPPORTED) */
-  int use_roulette;           /* must be 0 (UD_ERR_UNSUPPORTED) */
+  int use_directional_light;  /* must be 0 (UD_ERR_UNSUPPORTED): see ud_plb_render_set_light */
+  int use_roulette;           /* must be 0 (UD_ERR_UNSUPPORTED): see ud_plb_render_set_light */
   int n_primitives;           /* 0 .. UD_PLB_RENDER_MAX_PRIM */
   int prim_kind[UD_PLB_RENDER_MAX_PRIM];         /* as ud_plb_conf.prim_kind, 0 .. 6 */
   double prim_radius[UD_PLB_RENDER_MAX_PRIM];    /* Sphere / Capsule / RollingPin / Chopsticks radius */
@@ -804,6 +825,12 @@ typedef struct ud_plb_render_conf {
 } ud_plb_render_conf;
 int ud_plb_render_create(const ud_plb_render_conf* conf, ud_plb_render** out);
 int ud_plb_render_destroy(ud_plb_render* h);
+typedef struct ud_plb_render_light {
+  int use_directional_light;  /* cfg.RENDERER.use_directional_light (default off; envs/torus.yml: on) */
+  int use_roulette;           /* cfg.RENDERER.use_roulette (off everywhere in the reference) */
+  double light_direction[3];  /* cfg.RENDERER.light_direction, default (2, 1, 0.7); not normalised by the caller */
+} ud_plb_render_light;
+int ud_plb_render_set_light(ud_plb_render* h, const ud_plb_render_light* light);
 int ud_plb_render_bake(ud_plb_render* h, int B, const double* x, const int* color, float* bbox, int* status, void* stream);
 int ud_plb_render_read_volume(ud_plb_render* h, int B, long long* packed, float* sdf, void* stream);
 int ud_plb_render_gbuffer(ud_plb_render* h, int B, const double* prim_pos, const double* prim_rot, const double* prim_gap, int* kind,

@@ -25,7 +25,7 @@ SYMBOLS = [
     "ud_plb_grid_mass", "ud_plb_target_work_bytes", "ud_plb_target_sdf", "ud_plb_density_iou_work_bytes", "ud_plb_density_iou",
     "ud_plb_density_seq_work_bytes", "ud_plb_density_seq_sign_bytes", "ud_plb_density_seq_fwd", "ud_plb_density_seq_bwd", "ud_plb_chamfer",
     "ud_plb_policy_n_params", "ud_plb_policy_tape_bytes", "ud_plb_policy_fwd", "ud_plb_policy_bwd",
-    "ud_plb_render_create", "ud_plb_render_destroy", "ud_plb_render_bake", "ud_plb_render_read_volume", "ud_plb_render_gbuffer", "ud_plb_render_image",
+    "ud_plb_render_create", "ud_plb_render_destroy", "ud_plb_render_set_light", "ud_plb_render_bake", "ud_plb_render_read_volume", "ud_plb_render_gbuffer", "ud_plb_render_image",
     "ud_pc_fps", "ud_pc_ball_query", "ud_pc_group_fwd", "ud_pc_group_bwd",
     "ud_chamfer_fwd", "ud_chamfer_bwd", "ud_cloth_pnp_fwd", "ud_cloth_pnp_bwd", "ud_cloth_depth_fwd", "ud_cloth_depth_bwd",
     "ud_mpm_focus_fwd", "ud_mpm_focus_bwd", "ud_mpm_finish_fwd", "ud_mpm_finish_bwd",
@@ -74,6 +74,10 @@ class ud_plb_render_conf(C.Structure):
                 ("prim_kind", C.c_int * RENDER_MAX_PRIM), ("prim_radius", C.c_double * RENDER_MAX_PRIM), ("prim_h", C.c_double * RENDER_MAX_PRIM),
                 ("prim_shape", (C.c_double * 3) * RENDER_MAX_PRIM), ("prim_color", (C.c_float * 3) * RENDER_MAX_PRIM),
                 ("n_particles", C.c_int), ("max_envs", C.c_int)]
+
+
+class ud_plb_render_light(C.Structure):
+    _fields_ = [("use_directional_light", C.c_int), ("use_roulette", C.c_int), ("light_direction", C.c_double * 3)]
 
 
 def build(force: bool = False) -> str:
@@ -134,6 +138,7 @@ def lib():
         L.ud_plb_policy_bwd.argtypes = shape + [C.c_void_p, C.c_long] + [C.c_void_p] * 8
         L.ud_plb_render_create.argtypes = [C.c_void_p, C.c_void_p]
         L.ud_plb_render_destroy.argtypes = [C.c_void_p]
+        L.ud_plb_render_set_light.argtypes = [C.c_void_p, C.c_void_p]
         L.ud_plb_render_bake.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
         L.ud_plb_render_read_volume.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 3
         L.ud_plb_render_gbuffer.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 8

@@ -12,6 +12,10 @@
 // workgroup four tiles (16 x 16).  The image thread runs its spp samples one after the other and sums them in a register in the reference's
 // order, so nothing is atomic and the result is bit-identical from run to run.  Every loop is bounded (200 / 500 / 20 steps, max_ray_depth,
 // spp); no workgroup waits for another.
+//
+// The image kernel is compiled once per (directional light, roulette) -- the reference's two ti.static switches -- and the handle says which
+// instance a call runs (ud_plb_render_set_light); <false, false> is the kernel as it was before the switches existed.  The lit instances send
+// one shadow ray per bounce from the lanes that face the light, answered by render_occluded, an any-hit walk over next_hit's candidates.
 #include "common.h"
 #include "plb_prim.h"
 
@@ -40,6 +44,8 @@ struct ud_plb_render {
   float* bbox;        // [max_envs][2][3]
   int* status;        // [max_envs]
   double* prim;       // [max_envs][RP][PRIM_STRIDE]
+  int light, roulette;   // ud_plb_render_set_light: which instance of k_render_image runs
+  float light_dir[3];    // light_direction, rounded to f32 at the call
 };
 
 namespace ud {
@@ -346,6 +352,66 @@ __device__ void render_next_hit(const RenderK& k, const RenderEnv& e, const floa
   }
 }
 
+// The shadow ray of the directional light (renderer.py:383-384): true when next_hit(o, d) would return a distance <= 100.  next_hit takes a
+// candidate only when it lies below the closest so far, so its result is the smallest candidate and "closest > dist_limit" is "no candidate
+// <= 100": the candidates are tested in next_hit's order with next_hit's own conditions, the first one within reach ends the search, and no
+// normal or colour is fetched.
+__device__ bool render_occluded(const RenderK& k, const RenderEnv& e, const float* o, const float* d) {
+  if (d[2] != 0.0f) {                                   // background plane: part of the scene for a shadow ray too
+    const float rc = -(o[2] + 5.5f) / d[2];
+    if (rc > 0.0f && rc <= R_DIST_LIMIT) return true;
+  }
+  if (d[1] < 0.0f) {                                    // ground
+    const float gd = (o[1] + 0.002f) / (-d[1]);
+    if (gd < R_DIST_LIMIT) return true;
+  }
+  if (k.np > 0) {                                       // primitives
+    int j = 0;
+    float dist = 0.0f, sv = R_INF;
+    while (j < 200 && dist < R_DIST_LIMIT && sv > 1e-8f) {
+      const float pp[3] = {o[0] + dist * d[0], o[1] + dist * d[1], o[2] + dist * d[2]};
+      sv = R_INF;
+      for (int i = 0; i < k.np; ++i) sv = fminf(sv, render_prim_sdf(k, e, i, pp));
+      dist += sv;
+      ++j;
+    }
+    if (dist < R_DIST_LIMIT) return true;
+  }
+  bool hit = true;                                      // the body
+  float tn = -R_INF, tf = R_INF;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    if (d[i] == 0.0f) {
+      if (o[i] < e.b0[i] || o[i] > e.b1[i]) hit = false;
+    } else {
+      const float i1 = (e.b0[i] - o[i]) / d[i], i2 = (e.b1[i] - o[i]) / d[i];
+      tf = fminf(fmaxf(i1, i2), tf);
+      tn = fmaxf(fminf(i1, i2), tn);
+    }
+  }
+  if (tn > tf || !hit) return false;
+  tn = fmaxf(tn, 0.0f);
+  const float t0 = tn + 1e-4f;
+  float pos[3] = {o[0] + d[0] * t0, o[1] + d[1] * t0, o[2] + d[2] * t0};
+  float step[3] = {0.0f, 0.0f, 0.0f};
+  for (int j = 0; j < 500; ++j) {
+    const float s = render_sample_sdf(k, e, pos);
+    if (s < 0.0f) {
+      for (int l = 0; l < 20; ++l) {
+        step[0] = step[0] * 0.5f; step[1] = step[1] * 0.5f; step[2] = step[2] * 0.5f;
+        const float q[3] = {pos[0] - step[0], pos[1] - step[1], pos[2] - step[2]};
+        if (render_sample_sdf(k, e, q) < 0.0f) { pos[0] = q[0]; pos[1] = q[1]; pos[2] = q[2]; }
+      }
+      const float od[3] = {o[0] - pos[0], o[1] - pos[1], o[2] - pos[2]};
+      return render_norm(od) <= R_DIST_LIMIT;
+    }
+    const float m = fmaxf(s * 0.05f, 0.01f);
+    step[0] = d[0] * m; step[1] = d[1] * m; step[2] = d[2] * m;
+    pos[0] += step[0]; pos[1] += step[1]; pos[2] += step[2];
+  }
+  return false;
+}
+
 // ---------------------------------------------------------------- random draws, camera
 __device__ __forceinline__ unsigned render_lowbias32(unsigned x) {
   x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
@@ -404,6 +470,9 @@ __global__ void __launch_bounds__(256) k_render_gbuffer(ud_plb_render H, int* __
   for (int c = 0; c < 3; ++c) { normal[px * 3 + c] = h.n[c]; albedo[px * 3 + c] = h.c[c]; }
 }
 
+// LIGHT / ROULETTE: use_directional_light / use_roulette of the reference's trace, ti.static there and template parameters here;
+// <false, false> is the image of a handle whose light was never set.  Draws of bounce b: k = 2^30 + 4b + 0..2 the light noise, + 3 the roulette.
+template <bool LIGHT, bool ROULETTE>
 __global__ void __launch_bounds__(256) k_render_image(ud_plb_render H, int spp, unsigned seed, float* __restrict__ img) {
   const RenderK& k = H.k;
   int u, v;
@@ -417,6 +486,7 @@ __global__ void __launch_bounds__(256) k_render_image(ud_plb_render H, int spp, 
     const unsigned pixel = (unsigned)(u * k.img[1] + v);
     for (int s = 0; s < spp; ++s) {
       float pos[3] = {k.cam[0], k.cam[1], k.cam[2]}, d[3], thr[3] = {1.0f, 1.0f, 1.0f};
+      [[maybe_unused]] float contrib[3] = {0.0f, 0.0f, 0.0f};
       render_camera_ray(k, u, v, render_rand(seed, pixel, s, 0), render_rand(seed, pixel, s, 1), d);
       int depth = 0;
       while (depth < k.depth) {                          // trace (renderer.py:346-411), material always DIFFUSE
@@ -424,6 +494,7 @@ __global__ void __launch_bounds__(256) k_render_image(ud_plb_render H, int spp, 
         render_next_hit(k, e, pos, d, h);
         const float hp[3] = {pos[0] + h.t * d[0], pos[1] + h.t * d[1], pos[2] + h.t * d[2]};
         const unsigned kk = 2u + 4u * (unsigned)depth;
+        [[maybe_unused]] const unsigned kl = 0x40000000u + 4u * (unsigned)depth;
         ++depth;
         if (render_norm(h.n) != 0.0f) {
           float a[3] = {1.0f, 0.0f, 0.0f}, w[3];          // out_dir (renderer_utils.py:8-18)
@@ -445,15 +516,39 @@ __global__ void __launch_bounds__(256) k_render_image(ud_plb_render H, int spp, 
           render_normalize(d);
 #pragma unroll
           for (int c = 0; c < 3; ++c) { pos[c] = hp[c] + 1e-4f * d[c]; thr[c] = thr[c] * h.c[c]; }
+          if constexpr (LIGHT) {                         // :374-386, light_color = 1 (throughput * 1.0f is throughput)
+            float direct[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) direct[c] = H.light_dir[c] + (render_rand(seed, pixel, s, kl + c) - 0.5f) * 0.03f;
+            render_normalize(direct);
+            const float dot = (direct[0] * h.n[0] + direct[1] * h.n[1]) + direct[2] * h.n[2];
+            if (dot > 0.0f && !render_occluded(k, e, pos, direct))
+#pragma unroll
+              for (int c = 0; c < 3; ++c) contrib[c] += thr[c] * dot;
+          }
         } else {
           depth = k.depth;                               // the sky
         }
+        if constexpr (ROULETTE) {                        // :391-397, after every iteration, the sky's included; 0 / 0 as the reference's
+          const float mc = fmaxf(fmaxf(thr[0], thr[1]), thr[2]);
+          if (render_rand(seed, pixel, s, kl + 3u) > mc) {
+            depth = k.depth;
+            thr[0] = thr[1] = thr[2] = 0.0f;
+          } else {
+            thr[0] = thr[0] / mc; thr[1] = thr[1] / mc; thr[2] = thr[2] / mc;
+          }
+        }
       }
-      float c1 = ((d[0] * 0.8f + d[1] * 0.65f) + d[2] * 0.15f) * 0.5f + 0.5f;      // sky_color
-      c1 = fmaxf(fminf(c1, 1.0f), 0.0f);
-      const float sky[3] = {(c1 * 0.9f + (1.0f - c1) * 0.7f) * 1.5f, (c1 * 0.9f + (1.0f - c1) * 0.7f) * 1.5f, (c1 * 0.9f + (1.0f - c1) * 0.8f) * 1.5f};
+      if constexpr (LIGHT) {                             // :408-410: the sample is contrib, the sky term is not added
 #pragma unroll
-      for (int c = 0; c < 3; ++c) acc[c] += thr[c] * sky[c];
+        for (int c = 0; c < 3; ++c) acc[c] += contrib[c];
+      } else {
+        float c1 = ((d[0] * 0.8f + d[1] * 0.65f) + d[2] * 0.15f) * 0.5f + 0.5f;      // sky_color
+        c1 = fmaxf(fminf(c1, 1.0f), 0.0f);
+        const float sky[3] = {(c1 * 0.9f + (1.0f - c1) * 0.7f) * 1.5f, (c1 * 0.9f + (1.0f - c1) * 0.7f) * 1.5f, (c1 * 0.9f + (1.0f - c1) * 0.8f) * 1.5f};
+#pragma unroll
+        for (int c = 0; c < 3; ++c) acc[c] += thr[c] * sky[c];
+      }
     }
   }
   // copy (:414-426) and render_frame's img[:, ::-1].transpose(1, 0, 2): row = res1 - 1 - v, column = u
@@ -490,7 +585,7 @@ extern "C" {
 int ud_plb_render_create(const ud_plb_render_conf* c, ud_plb_render** out) {
   if (!c || !out) { set_error("ud_plb_render_create: null argument"); return UD_ERR_INVALID; }
   if (c->use_directional_light || c->use_roulette) {
-    set_error("ud_plb_render_create: use_directional_light / use_roulette are not covered (both are off in the reference's defaults and tasks)");
+    set_error("ud_plb_render_create: use_directional_light / use_roulette of the conf must be 0: lighting is handle state, see ud_plb_render_set_light");
     return UD_ERR_UNSUPPORTED;
   }
   if (!(c->dx > 0.0) || c->bake_size < 0 || c->n_particles < 1 || c->max_envs < 1 || c->spp < 1 || c->max_ray_depth < 1 || c->image_res[0] < 1 ||
@@ -550,6 +645,25 @@ int ud_plb_render_destroy(ud_plb_render* h) {
   return UD_OK;
 }
 
+int ud_plb_render_set_light(ud_plb_render* h, const ud_plb_render_light* l) {
+  if (!h || !l) { set_error("ud_plb_render_set_light: null argument"); return UD_ERR_INVALID; }
+  float dir[3];
+  for (int a = 0; a < 3; ++a) {
+    if (!(fabs(l->light_direction[a]) <= 3.4028234663852886e38)) {       // NaN, inf, or beyond the largest f32
+      set_error("ud_plb_render_set_light: light_direction (%g, %g, %g) is not finite in f32", l->light_direction[0], l->light_direction[1], l->light_direction[2]);
+      return UD_ERR_INVALID;
+    }
+    dir[a] = (float)l->light_direction[a];
+  }
+  if (l->use_directional_light && dir[0] == 0.0f && dir[1] == 0.0f && dir[2] == 0.0f) {
+    set_error("ud_plb_render_set_light: use_directional_light with a zero light_direction");
+    return UD_ERR_INVALID;
+  }
+  h->light = l->use_directional_light != 0; h->roulette = l->use_roulette != 0;
+  for (int a = 0; a < 3; ++a) h->light_dir[a] = dir[a];
+  return UD_OK;
+}
+
 int ud_plb_render_bake(ud_plb_render* h, int B, const double* x, const int* color, float* bbox, int* status, void* stream) {
   if (int rc = render_check_call("ud_plb_render_bake", h, B)) return rc;
   if (!x || !color || !bbox || !status) { set_error("ud_plb_render_bake: null x / color / bbox / status"); return UD_ERR_INVALID; }
@@ -592,7 +706,9 @@ int ud_plb_render_image(ud_plb_render* h, int B, const double* prim_pos, const d
   if (spp < 0 || spp > 65536) { set_error("ud_plb_render_image: spp=%d outside [0, 65536] (0 = the conf's)", spp); return UD_ERR_INVALID; }
   if (int rc = render_prims("ud_plb_render_image", h, B, prim_pos, prim_rot, prim_gap, (hipStream_t)stream)) return rc;
   const dim3 grid((h->k.img[0] + 15) / 16, (h->k.img[1] + 15) / 16, B);
-  hipLaunchKernelGGL(k_render_image, grid, dim3(256), 0, (hipStream_t)stream, *h, spp ? spp : h->spp, seed, img);
+  auto kern = h->light ? (h->roulette ? k_render_image<true, true> : k_render_image<true, false>)
+                       : (h->roulette ? k_render_image<false, true> : k_render_image<false, false>);
+  hipLaunchKernelGGL(kern, grid, dim3(256), 0, (hipStream_t)stream, *h, spp ? spp : h->spp, seed, img);
   UD_HIP_CHECK(hipGetLastError());
   return UD_OK;
 }

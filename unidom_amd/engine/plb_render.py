@@ -2,7 +2,8 @@
 the first-hit G-buffer and the path-traced image for B envs per call, in libunidom_hip.so (csrc/plb_render.hip; the contract is the
 ud_plb_render_* block of include/unidom_hip.h, the specification tests/plb_render_twin.py).
 
-Not covered: the directional light and Russian roulette (both off in the reference's defaults and in every task file: refused at create) and the
+The directional light (on in envs/torus.yml, off in the defaults and in the other task files) and Russian roulette (off everywhere) are state of the
+handle: PlbRenderer sets them from the RenderConf after create (set_light; the specification is tests/plb_render_light_twin.py).  Not covered: the
 `target` overlay (commented out in the reference).  The random draws are this project's own hash (ti.random cannot be pinned).
 """
 from __future__ import annotations
@@ -71,7 +72,7 @@ class PlbRenderer:
             dx=float(rc.dx), voxel_res=(C.c_int * 3)(*rc.voxel_res), bake_size=int(rc.bake_size), sdf_threshold=float(rc.sdf_threshold),
             image_res=(C.c_int * 2)(*rc.image_res), spp=int(rc.spp), max_ray_depth=int(rc.max_ray_depth),
             camera_pos=(C.c_double * 3)(*rc.camera_pos), camera_rot=(C.c_double * 2)(*rc.camera_rot),
-            use_directional_light=int(bool(rc.use_directional_light)), use_roulette=int(bool(rc.use_roulette)), n_primitives=P,
+            use_directional_light=0, use_roulette=0, n_primitives=P,      # lighting is handle state: set_light below
             prim_kind=(C.c_int * M)(*pad(getattr(sim_conf, "prim_kind", ()), 0)), prim_radius=(C.c_double * M)(*pad(sim_conf.prim_radius, 0.0)),
             prim_h=(C.c_double * M)(*pad(getattr(sim_conf, "prim_h", ()), 0.0)),
             prim_shape=(C.c_double * 3 * M)(*[(C.c_double * 3)(*(list(s) + [0.0] * 3)[:3]) for s in pad(getattr(sim_conf, "prim_shape", ()), (0.0, 0.0, 0.0))]),
@@ -82,6 +83,14 @@ class PlbRenderer:
         self._conf_rot = torch.tensor([tuple(map(float, q)) for q in rots], dtype=torch.float64, device=self.device).reshape(P, 4)
         self._h = C.c_void_p()
         _lib.check(_lib.lib().ud_plb_render_create(C.byref(cc), C.byref(self._h)), "ud_plb_render_create")
+        self.set_light(rc.use_directional_light, rc.use_roulette, rc.light_direction)
+
+    def set_light(self, use_directional_light, use_roulette=False, light_direction=None):
+        """ud_plb_render_set_light: which instance of the image kernel the next image() runs (host only).  light_direction None = the conf's."""
+        d = self.conf.light_direction if light_direction is None else light_direction
+        ll = _lib.ud_plb_render_light(use_directional_light=int(bool(use_directional_light)), use_roulette=int(bool(use_roulette)),
+                                      light_direction=(C.c_double * 3)(*map(float, d)))
+        _lib.check(_lib.lib().ud_plb_render_set_light(self._h, C.byref(ll)), "ud_plb_render_set_light")
 
     def __del__(self):
         try:

@@ -84,6 +84,15 @@ class PlbConf:
     action_scale_on_host = False
 
 
+class TorusConf(PlbConf):
+    """PlbConf (envs/torus.yml's SIMULATOR / SHAPES / PRIMITIVES) with the file's RENDERER block and colours: the directional light and the
+    camera the Torus experts of solve_action are drawn through (algorithms/plb_release.py).  PlbConf itself carries neither, so its render()
+    keeps the default camera and the sky light."""
+    particle_color = 100                      # SHAPES[0].color
+    prim_color = ((0.7, 0.7, 0.7), (0.7, 0.7, 0.7))   # PRIMITIVES[0..1].color
+    render_overrides = {"use_directional_light": True, "camera_pos": (0.5, 0.27, 2.5), "camera_rot": (0.0, 0.0)}   # RENDERER
+
+
 class MoveConf(PlbConf):
     """PlasticineLab/sim2sim/plb/envs/move.yml over sim2sim/plb/config/default_config.py, the env of the reference's identification runs:
     a 1000-particle rod lying on the floor and one Sphere at its end, action.scale 0.005.  E and nu are default_config's (the file sets
