@@ -111,7 +111,10 @@ int ud_cloth_launch_envs(const ud_cloth* h, int B);
  * since the previous call (0 = none; also 0 for handles that never take that path; ud_last_error() holds the text
  * otherwise) and resets the counter.  The rollout calls themselves stay asynchronous and return UD_OK. */
 int ud_cloth_poll_timeouts(ud_cloth* h, void* stream);
-/* bytes of the per-substep checkpoint arena a forward rollout of T macro steps x B envs writes */
+/* bytes of the per-substep checkpoint arena a forward rollout of T macro steps x B envs writes: the records of all envs,
+ * B * (T * substeps + 1) * (6 * Ppad + 8) floats, and behind them -- only where the one-workgroup restructured adjoint will
+ * run (a body of at most 512 padded particles, mode != 1) on at most 32 envs -- one 32-bit decision word per env, substep
+ * and padded particle, written by the forward call for the adjoint.  The same B and T must be given to both rollout calls. */
 size_t ud_cloth_ckpt_bytes(const ud_cloth* h, int B, int T);
 
 /* Forward: T macro steps (robot_step) of `substeps` substeps each, for B independent envs.

@@ -754,6 +754,13 @@ static int cloth_cluster_arena(ud_cloth* h, int B, hipStream_t stream, ud::Clust
   return UD_OK;
 }
 
+// The one-workgroup fast adjoint (cloth_launch_bwd_fast's dispatch condition below) on at most UD_CLOTH_DEC_MAX_B envs takes each substep's
+// discrete decisions from words behind the checkpoint's records (cloth_common.h).  The forward, the adjoint and ud_cloth_ckpt_bytes all
+// decide by this one function of the handle and B.
+static bool cloth_use_decisions(const ud_cloth* h, int B) {
+  return !cloth_use_cluster(h, B) && h->c.Pp <= 512 && h->mode != 1 && B <= UD_CLOTH_DEC_MAX_B;
+}
+
 extern "C" {
 
 int ud_cloth_create(const ud_cloth_conf* conf, const uint8_t* mask, ud_cloth** out) {
@@ -882,7 +889,8 @@ int ud_cloth_poll_timeouts(ud_cloth* h, void* stream) {
 
 size_t ud_cloth_ckpt_bytes(const ud_cloth* h, int B, int T) {
   if (!h || B < 0 || T < 0) return 0;
-  return (size_t)B * ud::cloth_env_records(T, h->c.S) * ud::cloth_rec_floats(h->c.Pp) * sizeof(float);
+  const size_t records = (size_t)B * ud::cloth_env_records(T, h->c.S) * ud::cloth_rec_floats(h->c.Pp);
+  return (records + (B >= 1 && cloth_use_decisions(h, B) ? ud::cloth_dec_words(B, T, h->c.S, h->c.Pp) : 0)) * sizeof(float);
 }
 
 int ud_cloth_rollout_fwd(ud_cloth* h, int B, int T, const float* x, const float* v, const float* prim,
@@ -923,6 +931,8 @@ int ud_cloth_rollout_fwd(ud_cloth* h, int B, int T, const float* x, const float*
     hipLaunchKernelGGL(ud::cloth_rollout_fwd_kernel<512>, dim3(B), dim3(h->c.Pp), shmem, (hipStream_t)stream, a);
   else
     hipLaunchKernelGGL(ud::cloth_rollout_fwd_kernel<1024>, dim3(B), dim3(h->c.Pp), shmem, (hipStream_t)stream, a);
+  if (ckpt && cloth_use_decisions(h, B))   // stream order: the pre-pass reads the records the kernel above wrote
+    ud::cloth_launch_decisions(h->c, B, T, (float*)ckpt, actions, (hipStream_t)stream);
   UD_HIP_CHECK(hipGetLastError());
   return UD_OK;
 }
@@ -956,8 +966,10 @@ int ud_cloth_rollout_bwd(ud_cloth* h, int B, int T, const void* ckpt, const floa
   } else if (h->c.Pp > 1024) {
     if (h->park_B < B) { ud::set_error("ud_cloth_rollout_bwd: the adjoint's scratch holds %d envs, %d asked", h->park_B, B); return UD_ERR_INVALID; }
     hipLaunchKernelGGL(ud::cloth_big_bwd_kernel, dim3(B), dim3(UD_BIG_T), shmem, (hipStream_t)stream, a, h->d_park);
-  } else if (h->mode != 1 && h->c.Pp <= 512)
+  } else if (h->mode != 1 && h->c.Pp <= 512) {
+    a.dec = cloth_use_decisions(h, B) ? 1 : 0;
     ud::cloth_launch_bwd_fast(a, (hipStream_t)stream);
+  }
   else if (h->c.Pp <= 512)
     hipLaunchKernelGGL(ud::cloth_rollout_bwd_kernel<512>, dim3(B), dim3(h->c.Pp), shmem, (hipStream_t)stream, a);
   else

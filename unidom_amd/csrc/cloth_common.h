@@ -38,14 +38,33 @@ struct ClothBwdArgs {
   const float *g_x, *g_v, *g_prim, *g_x_list, *g_v_list, *g_prim_list;
   int normalize;
   float *g_x0, *g_v0, *g_prim0, *g_actions, *g_k, *g_mu;
+  int dec;   // the checkpoint carries decision words (below): cloth_launch_bwd_fast runs the kernels that read them
 };
 
 
 // Checkpoint arena written by the forward kernels, read by the backward kernels:
 //   per env b: (T*S + 1) records of (6*Pp + 8) floats = x[3][Pp] | v[3][Pp] | primitive0[4] primitive1[4];
 //   record t*S+s is the INPUT state of substep (t,s); the last record is the final state.
+//   Behind the records of ALL envs, where the one-workgroup fast adjoint will run on at most UD_CLOTH_DEC_MAX_B envs (cloth.hip,
+//   cloth_use_decisions): B * T*S * Pp decision words, [b][t*S+s][lane] -- the discrete choices of substep (t,s) as the forward took
+//   them, written by cloth_decisions_kernel (cloth_fast_bwd.hip) right behind the forward kernel and read by the adjoint's sweep in
+//   place of re-deriving them.  The records' layout and per-env stride are the same with and without the words.
 __host__ __device__ inline size_t cloth_rec_floats(int Pp) { return (size_t)6 * Pp + 8; }
 __host__ __device__ inline size_t cloth_env_records(int T, int S) { return (size_t)T * S + 1; }
+__host__ __device__ inline size_t cloth_dec_words(int B, int T, int S, int Pp) { return (size_t)B * T * S * Pp; }
+
+// One decision word (all factors are discrete; no float leaves the sweep, so no rounding can move):
+//   bits  0-7, 8-15, 16-23   2 * clip_grad_01(x2[d]), d = 0, 1, 2: 0 / 1 / 2 (byte fields: v_cvt_f32_ubyteN, times 0.5, both exact)
+//   bits 24, 25, 26          |v_{n+1}[d]| < max_v
+//   bit  27, 28              the particle is held by gripper 0, gripper 1
+//   bits 29-30               lanes 0-7 only: 2 * clip_grad_01 of this lane's component of the moved primitives
+// A padding lane (i >= P) holds 0 in every particle field.
+constexpr int UD_DEC_DV = 24, UD_DEC_M0 = 27, UD_DEC_M1 = 28, UD_DEC_PRIM = 29;
+// Largest B that takes the decisions path: the pre-pass streams every record once, so its time grows with B, while the sweep's
+// saving does not (envs run side by side).  Measured table: profiles/r12_ablation.txt, DESIGN.md 3.1.
+#ifndef UD_CLOTH_DEC_MAX_B
+#define UD_CLOTH_DEC_MAX_B 32
+#endif
 
 // The grasp test |x - pos| <= radius (cloth_simulator.py:201,213) without a per-particle square root.  IEEE sqrtf
 // is monotone, so  sqrtf(s) <= r  <=>  s <= T(r)  where T(r) is the largest float whose correctly rounded root is
@@ -107,5 +126,6 @@ bool cloth_ref_fast_ok(const ClothConst& c);                                   /
 void cloth_launch_fwd_ref(const ClothFwdArgs& a, hipStream_t stream);
 void cloth_launch_fwd_fast(const ClothFwdArgs& a, hipStream_t stream);
 void cloth_launch_bwd_fast(const ClothBwdArgs& a, hipStream_t stream);
+void cloth_launch_decisions(const ClothConst& c, int B, int T, float* ckpt, const float* actions, hipStream_t stream);   // cloth_fast_bwd.hip
 
 }  // namespace ud

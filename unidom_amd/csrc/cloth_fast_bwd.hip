@@ -80,7 +80,17 @@ constexpr int UD_CLOTH_MAXP = 1024 + 1;   // LDS plane stride (floats; the kerne
 // branch on `normalize`, and the primitive cotangent's pieces run in every wave -- it is zero outside lanes 0-7 of wave 0 and stays
 // zero), so the scheduler can start the position reads of force_pairs_x under the norm chain.
 // FULL = the body fills its waves (P == Pp, fold_cloth1's 512 particles): no padding lane, so `live` is a constant and its selects go.
-template <bool NORM, bool FULL>
+// DEC = the substep's discrete decisions (grasp masks, the clip factors of x2, of v5 and of the primitives) come from the checkpoint's
+// decision words (cloth_common.h; cloth_decisions_kernel below computes them with the functions the DEC = false code calls in its loop)
+// and not from grip_own / clip_grad_01 / the compare with max_v: one word per lane-substep, fetched one substep ahead like nx / nv.
+// Every operation on a cotangent is the same in both; a select against zero becomes an AND with an all-ones / zero mask (same bits).
+__device__ __forceinline__ float and_mask(float x, int m) { return __builtin_bit_cast(float, __builtin_bit_cast(int, x) & m); }
+// m ? x : y for an all-ones / zero mask (v_bfi_b32)
+__device__ __forceinline__ float sel_mask(int m, float x, float y) {
+  return __builtin_bit_cast(float, (__builtin_bit_cast(int, x) & m) | (__builtin_bit_cast(int, y) & ~m));
+}
+
+template <bool NORM, bool FULL, bool DEC>
 __device__ __forceinline__ void cloth_rollout_bwd_fast(const ClothBwdArgs& a, float* ldsf) {
   // ldsf: Xs[3][MAXP] | Gs[3][MAXP] | red[2][16][UD_RSTR] | mac[16*8]
   const ClothConst c = a.c;
@@ -113,22 +123,32 @@ __device__ __forceinline__ void cloth_rollout_bwd_fast(const ClothBwdArgs& a, fl
   const size_t rec = cloth_rec_floats(Pp);
   const float* ck = a.ckpt + (size_t)b * cloth_env_records(T, S) * rec;
   GraspThr th0, th1;   // from record 0 = the rollout's input primitives, exactly what the forward derived them from
-  th0.init(ck[6 * Pp + 3]); th1.init(ck[6 * Pp + 7]);
+  if (!DEC) { th0.init(ck[6 * Pp + 3]); th1.init(ck[6 * Pp + 7]); }
   // records: `cur` = input of the substep being reversed, `vnext` = v of the record after it (= clip(v5))
   // The primitive rows of the records are read through the constant address space (scalar loads into SGPRs: the
   // checkpoints are read-only for this kernel), one substep ahead like the particle rows (`nps`, handed to `ps` after barrier 2).
   typedef const __attribute__((address_space(4))) float* cfptr;
   float vnext[3], nx[3], nv[3], ps[8], psl, nps[8], npsl;   // n* = the record the loop consumes next, fetched one substep ahead
+  // DEC: this env's decision words [T*S][Pp]; `ndw` = the word of the substep the loop reverses next (vnext, ps, psl and their n* stay unused)
+  const unsigned* const dw0 = (const unsigned*)(a.ckpt + (size_t)B * cloth_env_records(T, S) * rec) + (size_t)b * T * S * Pp;
+  const unsigned* dp = dw0 + ((size_t)T * S - 1) * Pp;
+  unsigned ndw = 0;
   {
     const float* r = ck + (size_t)T * S * rec;
+    if (!DEC) {
 #pragma unroll
-    for (int d = 0; d < 3; ++d) vnext[d] = r[(3 + d) * Pp + i];
+      for (int d = 0; d < 3; ++d) vnext[d] = r[(3 + d) * Pp + i];
+    }
     r = ck + ((size_t)T * S - 1) * rec;
 #pragma unroll
     for (int d = 0; d < 3; ++d) { nx[d] = r[d * Pp + i]; nv[d] = r[(3 + d) * Pp + i]; }
+    if (!DEC) {
 #pragma unroll
-    for (int d = 0; d < 8; ++d) ps[d] = ((cfptr)r)[6 * Pp + d];
-    psl = r[6 * Pp + (i & 7)];
+      for (int d = 0; d < 8; ++d) ps[d] = ((cfptr)r)[6 * Pp + d];
+      psl = r[6 * Pp + (i & 7)];
+    } else {
+      ndw = dp[i];
+    }
   }
   for (int q = i; q < 2 * 16 * UD_RSTR; q += Pp) red[q] = 0.f;   // slots of waves this launch does not have are read as zeros
   __syncthreads();
@@ -165,24 +185,43 @@ __device__ __forceinline__ void cloth_rollout_bwd_fast(const ClothBwdArgs& a, fl
         const float* r = rp;
 #pragma unroll
         for (int d = 0; d < 3; ++d) { nx[d] = r[(unsigned)(d * Pp + i)]; nv[d] = r[(unsigned)((3 + d) * Pp + i)]; }
+        if (!DEC) {
 #pragma unroll
-        for (int d = 0; d < 8; ++d) nps[d] = ((cfptr)r)[6 * Pp + d];
-        npsl = r[(unsigned)(6 * Pp + (i & 7))];
+          for (int d = 0; d < 8; ++d) nps[d] = ((cfptr)r)[6 * Pp + d];
+          npsl = r[(unsigned)(6 * Pp + (i & 7))];
+        }
+      }
+      const unsigned dw = ndw;
+      if (DEC) {
+        dp = (dp != dw0) ? dp - Pp : dp;
+        ndw = dp[i];
       }
       const unsigned par = step & 1u;
       float* rd = red + par * 16 * UD_RSTR;
       Xs[i] = x[0]; Xs[UD_CLOTH_MAXP + i] = x[1]; Xs[2 * UD_CLOTH_MAXP + i] = x[2];
       // ---- own-particle forward pieces and the nine sums (no neighbour data needed) ----
-      bool m0, m1;
-      float x2[3];
-      grip_own(x, ps, act, th0.at(t == 0 && s == 0), th1.at(t == 0 && s == 0), m0, m1, x2);
-      m0 = m0 && live; m1 = m1 && live;
+      bool m0 = false, m1 = false;
+      int M0 = 0, M1 = 0;   // DEC: the masks as all ones / zero (a padding lane's word is 0, so `live` is in them)
       float av[3], bv[3], bx[3];
+      if (DEC) {
+        M0 = (int)(dw << (31 - UD_DEC_M0)) >> 31;
+        M1 = (int)(dw << (31 - UD_DEC_M1)) >> 31;
 #pragma unroll
-      for (int d = 0; d < 3; ++d) {
-        const float Dx = clip_grad_01(x2[d]);
-        const float Dv = (fabsf(vnext[d]) < c.max_v) ? 1.f : 0.f;
-        av[d] = Dx * gx[d]; bv[d] = Dv * gv[d]; bx[d] = Dv * gx[d];
+        for (int d = 0; d < 3; ++d) {
+          const float Dx = (float)((dw >> (8 * d)) & 0xFFu) * 0.5f;
+          const float Dv = (float)((dw >> (UD_DEC_DV + d)) & 1u);
+          av[d] = Dx * gx[d]; bv[d] = Dv * gv[d]; bx[d] = Dv * gx[d];
+        }
+      } else {
+        float x2[3];
+        grip_own(x, ps, act, th0.at(t == 0 && s == 0), th1.at(t == 0 && s == 0), m0, m1, x2);
+        m0 = m0 && live; m1 = m1 && live;
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+          const float Dx = clip_grad_01(x2[d]);
+          const float Dv = (fabsf(vnext[d]) < c.max_v) ? 1.f : 0.f;
+          av[d] = Dx * gx[d]; bv[d] = Dv * gv[d]; bx[d] = Dv * gx[d];
+        }
       }
       float sm[UD_NSUM];
       sm[0] = dot3_m(gx[0], gx[1], gx[2], gx[0], gx[1], gx[2]);
@@ -191,7 +230,8 @@ __device__ __forceinline__ void cloth_rollout_bwd_fast(const ClothBwdArgs& a, fl
       sm[3] = (bv[0] * bv[0] + bv[1] * bv[1]) + bv[2] * bv[2];                      // three rounded products
       sm[4] = __builtin_fmaf(bv[1], bx[1], bv[0] * bx[0]) + bv[2] * bx[2];
       sm[5] = (bx[0] * bx[0] + bx[1] * bx[1]) + bx[2] * bx[2];
-      sm[6] = m1 ? sm[3] : 0.f; sm[7] = m1 ? sm[4] : 0.f; sm[8] = m1 ? sm[5] : 0.f;
+      if (DEC) { sm[6] = and_mask(sm[3], M1); sm[7] = and_mask(sm[4], M1); sm[8] = and_mask(sm[5], M1); m1 = M1 != 0; }
+      else { sm[6] = m1 ? sm[3] : 0.f; sm[7] = m1 ? sm[4] : 0.f; sm[8] = m1 ? sm[5] : 0.f; }
       if (NORM) {
         const float sm8[8] = {sm[0], sm[1], sm[2], sm[3], sm[4], sm[5], sm[6], sm[7]};
         const float w8 = wave_sum8_t(sm8, lane);
@@ -240,7 +280,7 @@ __device__ __forceinline__ void cloth_rollout_bwd_fast(const ClothBwdArgs& a, fl
       force_pairs_x<UD_CLOTH_MAXP>(c, nbs, Xs, k, iL2, mu, x, v, v3, &in);
       if (LOSE) wp.drop();
 #pragma unroll
-      for (int d = 0; d < 3; ++d) v4[d] = v3[d] * (m0 ? act[3] : 1.f);   // the suction as a factor (sc0 of the gripper-0 block below): x * 1 = x bit for bit
+      for (int d = 0; d < 3; ++d) v4[d] = v3[d] * (DEC ? sel_mask(M0, act[3], 1.f) : (m0 ? act[3] : 1.f));   // the suction as a factor (sc0 of the gripper-0 block below): x * 1 = x bit for bit
       // ---- reverse: clip (:326-329) and the two grippers (:313-314) with their normalisations folded in ----
       float gx2n[3], gv5n[3];
 #pragma unroll
@@ -249,7 +289,7 @@ __device__ __forceinline__ void cloth_rollout_bwd_fast(const ClothBwdArgs& a, fl
         gv5n[d] = __builtin_fmaf(bv[d], sv, (c.dt * sx) * bx[d]) * sB;
       }
       {  // gripper 1, branch-free: masks as 0/1 factors
-        const float s1 = act[7], m1f = m1 ? 1.f : 0.f, sc1 = m1 ? s1 : 1.f, h1 = (1.f - s1) * m1f;
+        const float s1 = act[7], m1f = DEC ? and_mask(1.f, M1) : (m1 ? 1.f : 0.f), sc1 = DEC ? sel_mask(M1, s1, 1.f) : (m1 ? s1 : 1.f), h1 = (1.f - s1) * m1f;
         const float dotv = __builtin_fmaf(gv5n[2], v4[2], __builtin_fmaf(gv5n[1], v4[1], gv5n[0] * v4[0]));
         const float dotx = __builtin_fmaf(act[6], gx2n[2], __builtin_fmaf(act[4], gx2n[0], act[5] * gx2n[1]));
         ga[7] = __builtin_fmaf(dotv - dotx, m1f, ga[7]);
@@ -260,7 +300,7 @@ __device__ __forceinline__ void cloth_rollout_bwd_fast(const ClothBwdArgs& a, fl
 #pragma unroll
       for (int d = 0; d < 3; ++d) { gxd[d] = gx2n[d] * s3x; gv3[d] = gv5n[d] * s3v; }
       {  // gripper 0
-        const float s0 = act[3], m0f = m0 ? 1.f : 0.f, sc0 = m0 ? s0 : 1.f, h0 = (1.f - s0) * m0f;
+        const float s0 = act[3], m0f = DEC ? and_mask(1.f, M0) : (m0 ? 1.f : 0.f), sc0 = DEC ? sel_mask(M0, s0, 1.f) : (m0 ? s0 : 1.f), h0 = (1.f - s0) * m0f;
         const float dotv = dot3_m(v3[0], v3[1], v3[2], gv3[0], gv3[1], gv3[2]);
         const float dotx = dot3_m(act[0], act[1], act[2], gxd[0], gxd[1], gxd[2]);
         ga[3] = __builtin_fmaf(dotv - dotx, m0f, ga[3]);
@@ -268,7 +308,7 @@ __device__ __forceinline__ void cloth_rollout_bwd_fast(const ClothBwdArgs& a, fl
         for (int d = 0; d < 3; ++d) { ga[d] = __builtin_fmaf(h0, gxd[d], ga[d]); gv3[d] *= sc0; }
       }
       // primitives (:322-323), uniform; counted once (lane 0) in the action accumulators
-      gpl *= clip_grad_01(psl + addl);
+      gpl *= DEC ? (float)((dw >> UD_DEC_PRIM) & 3u) * 0.5f : clip_grad_01(psl + addl);
       gaP += pm3 ? gpl : 0.f;
       // ---- v3 = (v1 + F dt) damp ; ground friction (:281-290) ----
       float gF[3];
@@ -294,9 +334,11 @@ __device__ __forceinline__ void cloth_rollout_bwd_fast(const ClothBwdArgs& a, fl
       Gs[i] = gF[0]; Gs[UD_CLOTH_MAXP + i] = gF[1]; Gs[2 * UD_CLOTH_MAXP + i] = gF[2];
       if (LOSE) wp.up();
       __syncthreads();   // barrier 2: Gs visible
+      if (!DEC) {
 #pragma unroll
-      for (int d = 0; d < 8; ++d) ps[d] = nps[d];   // next substep's primitives
-      psl = npsl;
+        for (int d = 0; d < 8; ++d) ps[d] = nps[d];   // next substep's primitives
+        psl = npsl;
+      }
       // ---- spring adjoint, gather form: g_x_i = gxd + sum_l J_il (gF_j - gF_i) ----
       f2 A0 = {gxd[0], 0.f}, A1 = {gxd[1], 0.f}, A2 = {gxd[2], 0.f};
       f2 h0[4], h1[4], h2[4];
@@ -319,8 +361,10 @@ __device__ __forceinline__ void cloth_rollout_bwd_fast(const ClothBwdArgs& a, fl
       const float ax0 = A0.x + A0.y, ax1 = A1.x + A1.y, ax2 = A2.x + A2.y;
       gk += __builtin_fmaf(in.S2, gF[2], __builtin_fmaf(in.S0, gF[0], in.S1 * gF[1]));   // sum_l w_l (r_l . gF) = gF . S
       gx[0] = ax0; gx[1] = ax1; gx[2] = ax2;
+      if (!DEC) {
 #pragma unroll
-      for (int d = 0; d < 3; ++d) vnext[d] = v[d];   // this substep's input v is the previous substep's clip(v5)
+        for (int d = 0; d < 3; ++d) vnext[d] = v[d];   // this substep's input v is the previous substep's clip(v5)
+      }
       if (LOSE) wp.drop();
     }
     // macro-step boundary: robot_step's action transform (:168-169)
@@ -367,29 +411,103 @@ __device__ __forceinline__ void cloth_rollout_bwd_fast(const ClothBwdArgs& a, fl
 // cotangents, a body that fills its waves -- keeps the name it always had; `_ragged` = a body with padding lanes in its last wave.
 __global__ void __launch_bounds__(512) cloth_rollout_bwd_fast_ragged_kernel(ClothBwdArgs a) {
   extern __shared__ float ldsf[];
-  cloth_rollout_bwd_fast<true, false>(a, ldsf);
+  cloth_rollout_bwd_fast<true, false, false>(a, ldsf);
 }
 
 __global__ void __launch_bounds__(512) cloth_rollout_bwd_fast_ragged_raw_kernel(ClothBwdArgs a) {
   extern __shared__ float ldsf[];
-  cloth_rollout_bwd_fast<false, false>(a, ldsf);
+  cloth_rollout_bwd_fast<false, false, false>(a, ldsf);
 }
 
 __global__ void __launch_bounds__(512) cloth_rollout_bwd_fast_kernel(ClothBwdArgs a) {
   extern __shared__ float ldsf[];
-  cloth_rollout_bwd_fast<true, true>(a, ldsf);
+  cloth_rollout_bwd_fast<true, true, false>(a, ldsf);
 }
 
 __global__ void __launch_bounds__(512) cloth_rollout_bwd_fast_raw_kernel(ClothBwdArgs a) {
   extern __shared__ float ldsf[];
-  cloth_rollout_bwd_fast<false, true>(a, ldsf);
+  cloth_rollout_bwd_fast<false, true, false>(a, ldsf);
+}
+
+// the same four with the decisions read from the checkpoint's words (DEC)
+__global__ void __launch_bounds__(512) cloth_rollout_bwd_dec_ragged_kernel(ClothBwdArgs a) {
+  extern __shared__ float ldsf[];
+  cloth_rollout_bwd_fast<true, false, true>(a, ldsf);
+}
+
+__global__ void __launch_bounds__(512) cloth_rollout_bwd_dec_ragged_raw_kernel(ClothBwdArgs a) {
+  extern __shared__ float ldsf[];
+  cloth_rollout_bwd_fast<false, false, true>(a, ldsf);
+}
+
+__global__ void __launch_bounds__(512) cloth_rollout_bwd_dec_kernel(ClothBwdArgs a) {
+  extern __shared__ float ldsf[];
+  cloth_rollout_bwd_fast<true, true, true>(a, ldsf);
+}
+
+__global__ void __launch_bounds__(512) cloth_rollout_bwd_dec_raw_kernel(ClothBwdArgs a) {
+  extern __shared__ float ldsf[];
+  cloth_rollout_bwd_fast<false, true, true>(a, ldsf);
 }
 
 void cloth_launch_bwd_fast(const ClothBwdArgs& a, hipStream_t stream) {
   const size_t shmem = (size_t)(6 * UD_CLOTH_MAXP + 2 * 16 * UD_RSTR + 16 * 8) * sizeof(float);
   auto* kern = a.c.P == a.c.Pp ? (a.normalize ? cloth_rollout_bwd_fast_kernel : cloth_rollout_bwd_fast_raw_kernel)
                                : (a.normalize ? cloth_rollout_bwd_fast_ragged_kernel : cloth_rollout_bwd_fast_ragged_raw_kernel);
+  if (a.dec)
+    kern = a.c.P == a.c.Pp ? (a.normalize ? cloth_rollout_bwd_dec_kernel : cloth_rollout_bwd_dec_raw_kernel)
+                           : (a.normalize ? cloth_rollout_bwd_dec_ragged_kernel : cloth_rollout_bwd_dec_ragged_raw_kernel);
   hipLaunchKernelGGL(kern, dim3(a.B), dim3(a.c.Pp), shmem, stream, a);
+}
+
+// The pre-pass: the decision words of all T*S substeps of all envs at once, on the whole chip, from the records the forward has just
+// written.  It calls what the DEC = false sweep calls per substep -- macro_action_f, GraspThr from record 0 (the first-substep threshold
+// for record 0), grip_own, clip_grad_01, the compare of record n + 1's v with max_v, and in lanes 0-7 clip_grad_01 of the moved primitive
+// component -- in this translation unit (contraction off), so the booleans are that sweep's by construction.
+// One workgroup of Pp lanes per (env, UD_DEC_RECS consecutive records): the two thresholds (a walk over IEEE square roots) are derived once
+// per workgroup, not once per word.
+constexpr int UD_DEC_RECS = 8;
+__global__ void __launch_bounds__(512) cloth_decisions_kernel(ClothConst c, int B, int T, float* ckpt, const float* actions) {
+  const int i = threadIdx.x, b = blockIdx.y;
+  const int P = c.P, Pp = c.Pp, S = c.S, TS = T * S;
+  const size_t rec = cloth_rec_floats(Pp);
+  const float* ck = ckpt + (size_t)b * cloth_env_records(T, S) * rec;
+  unsigned* words = (unsigned*)(ckpt + (size_t)B * cloth_env_records(T, S) * rec) + (size_t)b * TS * Pp;
+  GraspThr th0, th1;
+  th0.init(ck[6 * Pp + 3]); th1.init(ck[6 * Pp + 7]);
+  const bool live = i < P;
+  const bool pm3 = (i < 8) && ((i & 3) < 3);
+  const int n0 = blockIdx.x * UD_DEC_RECS, n1 = min(n0 + UD_DEC_RECS, TS);
+  for (int n = n0; n < n1; ++n) {
+    const float* r = ck + (size_t)n * rec;
+    const float* a8 = actions + ((size_t)(n / S) * B + b) * 8;
+    float act[8], x[3], ps[8], x2[3];
+    macro_action_f(a8, act);
+#pragma unroll
+    for (int d = 0; d < 3; ++d) x[d] = r[d * Pp + i];
+#pragma unroll
+    for (int d = 0; d < 8; ++d) ps[d] = r[6 * Pp + d];
+    bool m0, m1;
+    grip_own(x, ps, act, th0.at(n == 0), th1.at(n == 0), m0, m1, x2);
+    unsigned w = 0;
+    if (live) {
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        w |= (unsigned)(2.f * clip_grad_01(x2[d])) << (8 * d);
+        w |= (fabsf(r[rec + (3 + d) * Pp + i]) < c.max_v ? 1u : 0u) << (UD_DEC_DV + d);
+      }
+      w |= (m0 ? 1u : 0u) << UD_DEC_M0 | (m1 ? 1u : 0u) << UD_DEC_M1;
+    }
+    if (i < 8) {
+      const float addl = pm3 ? clipf(a8[i & 7], -2.0f, 2.0f) * (1.0f / 50.0f) : 0.f;
+      w |= (unsigned)(2.f * clip_grad_01(r[6 * Pp + (i & 7)] + addl)) << UD_DEC_PRIM;
+    }
+    words[(size_t)n * Pp + i] = w;
+  }
+}
+
+void cloth_launch_decisions(const ClothConst& c, int B, int T, float* ckpt, const float* actions, hipStream_t stream) {
+  hipLaunchKernelGGL(cloth_decisions_kernel, dim3((T * c.S + UD_DEC_RECS - 1) / UD_DEC_RECS, B), dim3(c.Pp), 0, stream, c, B, T, ckpt, actions);
 }
 
 }  // namespace ud
