@@ -841,6 +841,92 @@ int ud_plb_render_gbuffer(ud_plb_render* h, int B, const double* prim_pos, const
 int ud_plb_render_image(ud_plb_render* h, int B, const double* prim_pos, const double* prim_rot, const double* prim_gap, int spp,
                         unsigned int seed, float* img, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Cloth renderer: MeshPyRenderer.render (daxbench/core/engine/pyrender/py_render.py:16-117) for M frames per call: the cloth's
+ * triangle mesh (two-sided), S analytic spheres per frame (the gripper) and the ground rectangle, seen by the reference's camera.
+ * A handle of its own; ud_cloth_conf is not involved.  f32 throughout.  The operation order written below IS the contract:
+ * tests/cloth_render_twin.py restates it in NumPy f32, is the specification, and is bit-equal in colour, depth and triangle id.
+ * Camera, projection, coverage, depth, mirror and channel order are the reference's.  UNPINNED by reference data (pyrender, OpenGL
+ * and the wood texture cannot be had beside this library; nothing of the reference's was ever rendered for comparison):
+ *   - the SHADING is this project's own (pyrender's PBR shader is not restated): flat normals, Lambert, the reference's three lights;
+ *   - the ground is one flat colour, not wood_uv.png;
+ *   - the gripper is an analytic sphere, not the reference's icosphere with random face colours;
+ *   - a triangle with a vertex nearer than znear is dropped whole, not clipped (the cloth never comes within 0.05 of this camera).
+ * Every a*b+c below is a rounded multiply, then a rounded add; divisions and square roots are correctly rounded; sums of three
+ * are (a + b) + c.  Only + - * / sqrt min max floor ceil and comparisons occur.
+ *
+ * Frames.  The render frame is z-up: a sim point (x, y, z) is the render point (x, z, y) (py_render.py:83); vertices and sphere
+ *   centres are passed in sim order and swapped here.  conf positions (camera, ground) are in the render frame.
+ * Constants, formed in f64 at create and rounded to f32 once: look_at (:50-70) z = normalize(camera_pos - camera_target), x =
+ *   normalize(cross(camera_up, z)), y = cross(z, x) -> R (rows x, y, z), P = camera_pos; t = tan(yfov / 2); fy = (height / 2) / t;
+ *   fx = (width / 2) / ((width / height) t); cx = width / 2; cy = height / 2; cos_outer = cos(pi / 6); cos_range = cos(pi / 16) -
+ *   cos(pi / 6); inv_pi = 1 / pi.  The light pose is the camera pose (the reference's cam_pose = None).
+ * eye(p), p in the render frame: q = p - P; (R[r][0] q0 + R[r][1] q1) + R[r][2] q2 for r = 0, 1, 2.  The camera looks along -z.
+ * Setup, per vertex: (xe, ye, ze) = eye; d = -ze; sx = cx + (fx xe) / d; sy = cy - (fy ye) / d.
+ * Pixel (row v, column u) of the unmirrored image, row 0 at the top: px = u + 0.5, py = v + 0.5; its ray in the eye frame is
+ *   t (rx, ry, -1) with rx = (px - cx) / fx, ry = (cy - py) / fy, so t is the depth (-z_eye).
+ * Mesh.  Triangle i with vertices A, B, C (indices ia, ib, ic):
+ *   dropped when any d < znear (not d >= znear); area = (Bx - Ax)(Cy - Ay) - (By - Ay)(Cx - Ax) on (sx, sy); dropped when area is
+ *   not < 0 or > 0; s = sign(area).  Candidate pixels: ceil(min sx - 0.5) <= u <= floor(max sx - 0.5), the same in v with sy.
+ *   edge(p -> q) at (px, py), with (p', q') = (p, q) when index(p) < index(q), else (q, p): e = (q'x - p'x)(py - p'y) - (q'y -
+ *   p'y)(px - p'x), negated when the ends were swapped -- so the two triangles that share an edge compute exact negatives and the
+ *   inclusive test below leaves no hole.  e0 = edge(B -> C), e1 = edge(C -> A), e2 = edge(A -> B).  Covered when s e0 >= 0, s e1
+ *   >= 0, s e2 >= 0 and s esum > 0 with esum = (e0 + e1) + e2 (the doubled area, as the sum the barycentrics b_i = e_i / esum are
+ *   normalised by: they add up to one to a rounding, which b_i = e_i / area does not for sub-pixel triangles).
+ *   depth = esum / ((e0 / dA + e1 / dB) + e2 / dC) (perspective-correct: 1 / sum b_i / d_i); taken when depth >= znear.  The nearest
+ *   depth wins, on equal depth bits the lower triangle index.
+ * Spheres j = 0 .. S-1 (centre in sim order, radius r; r <= 0: absent): c = eye(centre); qa = (rx rx + ry ry) + 1; tc = ((rx cx
+ *   + ry cy) - cz) / qa; q = (cx - tc rx, cy - tc ry, cz + tc); h2 = r r - ((qx qx + qy qy) + qz qz); hit when h2 >= 0; ts = tc -
+ *   sqrt(h2 / qa), taken when ts >= znear (the near root only) and the pixel holds nothing yet or ts < the depth it holds (so the
+ *   mesh and the earlier sphere keep an exact tie); normal ((ts rx - cx) / r, (ts ry - cy) / r, (-ts - cz) / r).
+ * Ground, in the render frame: D[c] = (R[0][c] rx + R[1][c] ry) - R[2][c]; when D2 < 0: tg = (ground_z - P2) / D2; hx = P0 + tg D0;
+ *   hy = P1 + tg D1; taken when tg >= znear, ground_min <= (hx, hy) <= ground_max and the pixel holds nothing or tg < its depth.
+ *   Normal: the third column of R.
+ * Shading of the winner at e = (depth rx, depth ry, -depth): mesh normal n = cross(B - A, C - A) of the eye positions, divided by
+ *   its length sqrt((n0 n0 + n1 n1) + n2 n2) ((0, 0, 1) when that is 0).  ne = (n0 e0 + n1 e1) + n2 e2; ne > 0: n = -n.
+ *   ndl_d = max(n2, 0); r2 = (e0 e0 + e1 e1) + e2 e2; rl = sqrt(r2); ndl_s = max(-((n0 e0 + n1 e1) + n2 e2) / rl, 0);
+ *   cosang = -e2 / rl; s = min(max((cosang - cos_outer) / cos_range, 0), 1); spot = (s s)(3 - 2 s);
+ *   lit = 0.05 + (1 ndl_d + ((10 spot) ndl_s) / r2) inv_pi   (ambient 0.05; directional light 1 along -z; spot light 10 at the eye,
+ *   inner cone pi / 16, outer pi / 6, inverse-square);  channel = base * lit; u8 = (int)(min(max(channel, 0), 1) * 255 + 0.5).
+ *   Nothing hit: white, depth 0.
+ * Outputs, in the orientation py_render.py:110-111 returns: color [M,H,W,3] u8 mirrored left-right with the channels reversed
+ *   (pixel (v, u) lands at [v, W-1-u] as B, G, R), depth [M,H,W] f32 mirrored the same way, and tri [M,H,W] i32 (NULL: not
+ *   written): the winning triangle index, -1 nothing, -2 a sphere, -3 the ground.
+ *
+ * ud_cloth_render_create: faces is a HOST array [n_faces,3] of vertex indices, copied into the handle.  A null argument, a size
+ *   below 1 (n_faces, n_spheres: below 0), yfov outside (0, pi), znear <= 0, a degenerate look_at or a face index outside [0,
+ *   n_vertices): UD_ERR_INVALID.  width or height > 4096, n_vertices or n_faces > 2^20, n_spheres > 16, max_frames > 65535 or
+ *   max_frames * n_vertices >= 2^31 - 256: UD_ERR_UNSUPPORTED.  Arena: 20 B per vertex and frame, allocated here for max_frames.
+ * ud_cloth_render_frames: vertices [M,n_vertices,3], spheres [M,n_spheres,4] (NULL when n_spheres = 0), device arrays.  Two
+ *   launches, no allocation, no host synchronisation.  A null handle / vertices / color / depth (spheres with n_spheres > 0), M < 1
+ *   or M > max_frames: UD_ERR_INVALID, nothing launched, no output touched.  Results are bit-identical from run to run.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct ud_cloth_render ud_cloth_render;
+/* (a tagged struct: the generated binding stub of INTEGRATION.md lists the three simulator confs) */
+typedef struct ud_cloth_render_conf {
+  int width;                  /* 640 */
+  int height;                 /* 480 */
+  double yfov;                /* pi / 3 */
+  double znear;               /* 0.05 (pyrender's default); no far plane */
+  double camera_pos[3];       /* (0.9, 0.5, 1.0), render frame; also the pose of both lights */
+  double camera_target[3];    /* (0.6, 0.5, 0.0) */
+  double camera_up[3];        /* (0, 0, 1) */
+  double ground_min[2];       /* (-0.02, -0.04): wood.obj scaled to 1 x 1 and moved to (0.48, 0.46, -0.02) */
+  double ground_max[2];       /* (0.98, 0.96) */
+  double ground_z;            /* -0.02 */
+  float cloth_color[3];       /* base colours, RGB in [0, 1] */
+  float ground_color[3];
+  float sphere_color[3];
+  int n_vertices;             /* V of every call */
+  int n_faces;                /* F */
+  int n_spheres;              /* S >= 0 spheres per frame */
+  int max_frames;             /* arenas are allocated for this many frames; a call with more returns UD_ERR_INVALID */
+} ud_cloth_render_conf;
+int ud_cloth_render_create(const ud_cloth_render_conf* conf, const int* faces, ud_cloth_render** out);
+int ud_cloth_render_destroy(ud_cloth_render* h);
+int ud_cloth_render_frames(ud_cloth_render* h, int M, const float* vertices, const float* spheres, unsigned char* color, float* depth,
+                           int* tri, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,10 @@ parameter-aware observation):
     step_diff               :201-231    get_collision_func  :239-243
 The reference jit-compiles step_diff around lax.scan(simulator.step_jax); here the scan is one kernel launch
 (ClothSimulator.rollout) and the surrounding reward / observation arithmetic is torch on the same stream.
-Rendering (pyrender) is out of scope: step_with_render / render raise NotImplementedError.
+    render / step_with_render :189-199, :233-234   (MeshPyRenderer, core/engine/pyrender/py_render.py:16-117)
+Rendering is a triangle rasteriser on the device (engine/cloth_render.py, csrc/cloth_render.hip): the reference's camera, projection,
+depth and image orientation; the shading is this project's own (pyrender is not restated).  The renderer handle is created by the first
+render call: an env that never renders allocates nothing for it.
 """
 from __future__ import annotations
 
@@ -159,11 +162,36 @@ class ClothEnv:
 
         return step_diff
 
-    def step_with_render(self, actions, state, visualize=True):
-        raise NotImplementedError("rendering (pyrender) is outside the hot path; see DESIGN.md")
+    # ------------------------------------------------------------------------------------------------
+    def _renderer(self):
+        if getattr(self, "_cloth_renderer", None) is None:      # created on the first render call
+            from ...engine.cloth_render import ClothRenderer
+            self._cloth_renderer = ClothRenderer(self.simulator, getattr(self.conf, "render_conf", None))
+        return self._cloth_renderer
+
+    def render_batch(self, state, want_tri=False):
+        """The camera view of every leading index of a state ([B]) or a state list ([T,B]), one call: device tensors
+        (color u8 [..., 480, 640, 3] mirrored left-right in BGR as the reference returns it, depth f32 [..., 480, 640])."""
+        x = state.x.detach()
+        lead = tuple(x.shape[:-2])
+        x_grid = self.simulator.get_x_grid(x.reshape((-1,) + tuple(x.shape[-2:])))
+        return self._renderer().frames(x_grid.reshape(lead + tuple(x_grid.shape[1:])), state.primitive0.detach(), want_tri=want_tri)
 
     def render(self, state, visualize=True):
-        raise NotImplementedError("rendering (pyrender) is outside the hot path; see DESIGN.md")
+        """(color [480,640,3] u8, depth [480,640] f32) of env 0 as NumPy arrays (:233-234); `visualize` is accepted, there is no window."""
+        first = state._replace(x=state.x[:1], primitive0=state.primitive0[:1])
+        color, depth = self.render_batch(first)
+        return color[0].cpu().numpy(), depth[0].cpu().numpy()
+
+    def step_with_render(self, actions, state, visualize=True):
+        """step_diff, plus info["img_list"]: the 40 colour images of env 0, one per macro step (:189-199).  The reference simulates the
+        macro steps a second time from the old state to draw them; the rollout is deterministic, so step_diff's own state list is
+        the same thing and is rendered in one call."""
+        obs, reward, done, info = self.step_diff(actions, state, want_lists=True)
+        sl = info["state_list"]
+        color, _ = self.render_batch(sl._replace(x=sl.x[:, 0], primitive0=sl.primitive0[:, 0]))
+        info["img_list"] = list(color.cpu().numpy())
+        return obs, reward, done, info
 
     def create_cloth_mask(self, conf):
         raise NotImplementedError
