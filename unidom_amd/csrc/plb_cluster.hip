@@ -78,7 +78,7 @@ struct PclArgs {
   int keep;                            // forward: a checkpoint is written
   double* cg[3];                       // [Bl][G][4] rotating exchange grids: (m, mv) forward, cotangent of v_out backward (rest state: zero)
   unsigned* bar;                       // [Bl][PCL_BAR_STRIDE]: arrival counter, generation word, exit counter (rest state: zero)
-  double* gposacc;                     // [Bl][S+1][np][3] backward: cotangent of the primitive trajectory from the grid op (rest state: zero)
+  double* gposacc;                     // [Bl][S+1][np][3] backward: [s] = what the grid op of substep s sends to pos[s + 1] and, negated, to pos[s] (rest state: zero)
   double* gpar;                        // [Bl][4] backward: E, nu, yield stress, ground friction (rest state: zero)
   int* timeouts;                       // handle-wide count of parts that gave up waiting
 };
@@ -593,10 +593,9 @@ __global__ void __launch_bounds__(PCL_T) pcl_bwd_kernel(const PclArgs a) {
 #pragma unroll
         for (int kk = 0; kk < 3; ++kk) {
           const double qq = plb_wave_sum(qs[pi][kk]);
-          if (lead && qq != 0.0) {
-            __hip_atomic_fetch_add(gposacc + ((f + 1) * c.np + pi) * 3 + kk, qq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_fetch_add(gposacc + (f * c.np + pi) * 3 + kk, -qq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
+          // Q[f]: the sticky sphere's cells take (pos[f + 1] - pos[f]) / dt, so the sum goes to pos[f + 1] and, negated, to pos[f]; it is kept ONCE
+          // and the epilogue cancels it against itself where the bound clamp passes (two sums collected in two orders leave their round-off)
+          if (lead && qq != 0.0) __hip_atomic_fetch_add(gposacc + (f * c.np + pi) * 3 + kk, qq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
       }
       if (__any(gfric != 0.0)) {
@@ -682,17 +681,17 @@ __global__ void __launch_bounds__(PCL_T) pcl_bwd_kernel(const PclArgs a) {
         const double raw = (pi == 0) ? a.action[b * 3 + d] : 0.0;
         const double pv = (pi == 0) ? fmin(fmax(raw, -1.0), 1.0) / (double)S : 0.0;
         double gpv = 0.0;
-        double tot = pcl_ld(gposacc + (S * c.np + pi) * 3 + d) + (a.gpp ? a.gpp[((long)b * c.np + pi) * 3 + d] : 0.0);
-        pcl_st(gposacc + (S * c.np + pi) * 3 + d, 0.0);
+        // the cotangent of pos[s + 1] is r + Q[s] and that of pos[s] is Q[s - 1] - Q[s] + pass (r + Q[s]): where the clamp passes, Q[s] drops
+        // out exactly and r goes on unchanged; where it does not, -Q[s] is all that is left.  Q[-1] = 0: the start position gets r
+        double r = a.gpp ? a.gpp[((long)b * c.np + pi) * 3 + d] : 0.0;
         for (int s = S - 1; s >= 0; --s) {
-          const double un = s_pos[(s * c.np + pi) * 3 + d] + pv;
-          const double pass = (un >= c.lo[d] && un <= c.hi[d]) ? 1.0 : 0.0;
-          const double g = pass * tot;
-          gpv += g;
-          tot = pcl_ld(gposacc + (s * c.np + pi) * 3 + d) + g;
+          const double Q = pcl_ld(gposacc + (s * c.np + pi) * 3 + d);
           pcl_st(gposacc + (s * c.np + pi) * 3 + d, 0.0);
+          const double un = s_pos[(s * c.np + pi) * 3 + d] + pv;
+          if (un >= c.lo[d] && un <= c.hi[d]) gpv += r + Q;
+          else r = -Q;
         }
-        if (a.prim_o) a.prim_o[((long)b * c.np + pi) * 3 + d] = tot;
+        if (a.prim_o) a.prim_o[((long)b * c.np + pi) * 3 + d] = r;
         if (pi == 0 && a.g_action) a.g_action[b * 3 + d] = (raw >= -1.0 && raw <= 1.0) ? gpv / (double)S : 0.0;
       }
       if (tid >= 64 && tid < 68) {
