@@ -927,6 +927,105 @@ int ud_cloth_render_destroy(ud_cloth_render* h);
 int ud_cloth_render_frames(ud_cloth_render* h, int M, const float* vertices, const float* spheres, unsigned char* color, float* depth,
                            int* tri, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * MPM renderer: what the five MLS-MPM envs show (ParticlePyRenderer and WaterPyRenderer, py_render.py:120-174; the primitives of
+ * envs/basic/mpm_env.py:200-236) for M frames per call: one sphere (mode 0) or one screen-space point (mode 1) per particle, n_prims
+ * primitives of one kind (0 oriented box, 1 cut hollow sphere) and the ground rectangle, seen by the reference's camera (cam_pose is
+ * None in every MPM env: the cloth renderer's camera).  A handle of its own; ud_mpm_conf is not involved.  f32 throughout.  The
+ * operation order written below IS the contract: tests/mpm_render_twin.py restates it in NumPy f32 by brute force over all pixels, is
+ * the specification, and is bit-equal in colour, depth and id.
+ * The reference's: camera, projection, the sphere radius 0.008, the particle grey, the water colour and alpha, the one-pixel point,
+ * the unmirrored RGB orientation.  DEVIATIONS, none pinned by reference data (nothing of pyrender's was ever rendered for comparison):
+ *   - a particle is an analytic sphere, not a uv_sphere mesh;
+ *   - only the nearest point of a pixel blends (pyrender blends every layer in draw order);
+ *   - a primitive is drawn where the simulator collides with it, from the inverse transform of inv_trans_batch (primitives.py:105-109),
+ *     not through the reference's Euler-angle detour (as_euler('xyz'), negate [2], from_euler('zyx'));
+ *   - the cut hollow sphere is sphere-traced on its SDF, not drawn from a marching-cubes mesh;
+ *   - a particle nearer than the near plane is dropped whole, not clipped;
+ *   - the shading and the primitive / ground colours are this project's own (as for the cloth renderer); the ground is one flat colour.
+ * Frames, constants, eye(p), pixel rays (rx, ry), the ground, lit(n, e) and the u8 rounding are EXACTLY those of the ud_cloth_render
+ * block above.  Every a*b+c is a rounded multiply, then a rounded add; sums of three are (a + b) + c; only + - * / sqrt min max floor
+ * ceil fabs and comparisons occur.
+ *
+ * Further constants (f32): alpha = particle_color[3]; oma = 1 - alpha; half = point_size * 0.5; thresh = znear + radius (mode 0, one
+ *   f32 addition) or znear (mode 1).
+ * Setup, per particle (sim order (x, y, z)): (xe, ye, ze) = eye; d = -ze; sx = cx + (fx xe) / d; sy = cy - (fy ye) / d.  The particle
+ *   is DROPPED whole when a coordinate is not finite (|c| <= FLT_MAX fails) or d >= thresh fails.
+ * Particles, mode 0 (spheres of radius r = radius), per pixel and particle, the cloth block's sphere formulas with c = (xe, ye, -d):
+ *   qa = (rx rx + ry ry) + 1; tc = ((rx cx + ry cy) - cz) / qa; q = (cx - tc rx, cy - tc ry, cz + tc); h2 = r r - ((qx qx + qy qy)
+ *   + qz qz); hit when h2 >= 0; ts = tc - sqrt(h2 / qa), taken when ts >= znear.  The nearest ts wins, on equal depth bits the lower
+ *   particle index.  Normal ((ts rx - cx) / r, (ts ry - cy) / r, (-ts - cz) / r).
+ * Particles, mode 1 (points): with px = u + 0.5, py = v + 0.5 the particle covers the pixel when sx - half <= px < sx + half and
+ *   sy - half <= py < sy + half (each bound one f32 operation); its depth there is d.  The nearest wins, then the lower index.
+ * Primitives j = 0 .. n_prims-1 (position p, quaternion q = (w, x, y, z) of this frame, half sizes s_j from create).  Setup, per
+ *   (frame, primitive): c = (q0, -q1, -q2, -q3); nq = sqrt(((c0 c0 + c1 c1) + c2 c2) + c3 c3) + 1e-12; iq = c / nq;
+ *   qrot(iq, v): uv = (iq2 v2 - iq3 v1, iq3 v0 - iq1 v2, iq1 v1 - iq2 v0); w = (iq2 uv2 - iq3 uv1, iq3 uv0 - iq1 uv2, iq1 uv1 -
+ *   iq2 uv0); out_a = v_a + 2 (iq0 uv_a + w_a)  (primitives.py:95-102).  Column k of A is qrot(iq, unit vector k); the camera in the
+ *   local frame is o = qrot(iq, (P0 - p0, P2 - p1, P1 - p2)) (P is in the render frame; sim order swaps its last two).
+ *   Per pixel: the ray in the render frame is D[c] = (R[0][c] rx + R[1][c] ry) - R[2][c], in sim order Ds = (D0, D2, D1); in the local
+ *   frame dl_a = (A[a][0] Ds0 + A[a][1] Ds1) + A[a][2] Ds2; the point at depth t is o + t dl (o_a + t dl_a).
+ *   prim_kind 0, box: tnear = -inf, tfar = +inf, axis = 0; for a = 0, 1, 2: when dl_a == 0 the ray misses unless |o_a| <= s_a and the
+ *     axis is skipped; else t1 = (-s_a - o_a) / dl_a, t2 = (s_a - o_a) / dl_a, tn = min(t1, t2), tf = max(t1, t2); tn > tnear: tnear
+ *     = tn, axis = a; tfar = min(tfar, tf).  Hit when tnear <= tfar and tnear >= znear, at depth tnear.  Local normal: -1 on `axis`
+ *     when dl_axis > 0, else +1; 0 elsewhere.  A half size of 0 is a plate.
+ *   prim_kind 1, cut hollow sphere s = (r, h, t) (container.py:8-16 as csrc/mpm_collide.h::container_sdf_x states it): w = sqrt(r r -
+ *     h h); sdf(p): q0 = sqrt((p0 p0 + p2 p2) + 1e-12); q1 = p1; d0 = q0 - w; d1 = q1 - h; h q0 < w q1 ? sqrt((d0 d0 + d1 d1) + 1e-12)
+ *     - t : |sqrt((q0 q0 + q1 q1) + 1e-12) - r| - t.  Bounding sphere rb = r + t: aa = (dl0 dl0 + dl1 dl1) + dl2 dl2; bq = (o0 dl0 +
+ *     o1 dl1) + o2 dl2; tcb = -bq / aa; q = o + tcb dl; h2 = rb rb - ((q0 q0 + q1 q1) + q2 q2); miss unless h2 >= 0; hs = sqrt(h2 /
+ *     aa); tout = tcb + hs; tt = max(tcb - hs, znear); miss unless tt <= tout; len = sqrt(aa).  Then at most K = 64 times: v = sdf(o
+ *     + tt dl); v <= eps = 1e-4: hit at depth tt, stop; else tt = tt + v / len; tt <= tout fails: miss, stop.  No hit after K: miss.
+ *     Local normal: n_a = sdf(p + step e_a) - sdf(p - step e_a) at p = o + tt dl with step = 1e-4, divided by sqrt((n0 n0 + n1 n1) +
+ *     n2 n2) ((0, 0, 1) when that is 0).
+ *   Normal to the eye frame: ns_c = (A[0][c] nl0 + A[1][c] nl1) + A[2][c] nl2; n_r = (R[r][0] ns0 + R[r][1] ns2) + R[r][2] ns1.
+ * Nearest.  Mode 0: the pixel first holds its nearest sphere, if any.  Then the primitives in index order, then the ground, each
+ *   taken when the pixel holds nothing yet or its depth < the depth held: an exact tie is kept by particle, then primitive, then ground.
+ *   Mode 1: the same without the particles; then the pixel's nearest point is taken when the pixel holds nothing or d < the depth held.
+ * Colour.  bc = min(max(base lit, 0), 1) per channel of the opaque winner (base: particle_color RGB, prim_color, ground_color), 1 when
+ *   there is none.  A point that was taken is unlit: channel = alpha pc + oma bc.  u8 = (int)(min(max(channel, 0), 1) * 255 + 0.5).
+ * Outputs, NOT mirrored, as py_render.py:140-145 and :169-174 return them: color [M,H,W,3] u8 RGB, depth [M,H,W] f32 (the nearest
+ *   of everything, points included; 0 when nothing) and id [M,H,W] i32 (NULL: not written): >= 0 the particle index, -1 nothing, -3 the
+ *   ground, -4 - j primitive j.
+ * Unspecified image, never a fault: a non-finite primitive pose, coordinates beyond 1e18 in magnitude.
+ *
+ * ud_mpm_render_create: prim_sizes is a HOST array [n_prims,3] of half sizes (box) or (r, h, t) (cut hollow sphere), copied into the
+ *   handle (NULL when n_prims = 0).  A null argument, width / height / n_particles / max_frames < 1, n_prims < 0, yfov outside (0, pi),
+ *   znear <= 0, a degenerate look_at, mode or prim_kind outside {0, 1}, radius <= 0 in mode 0, point_size < 1: UD_ERR_INVALID.  width or
+ *   height > 4096, n_particles > 2^20, n_prims > 16, max_frames > 65535 or max_frames * n_particles >= 2^31 - 256: UD_ERR_UNSUPPORTED.
+ *   Arena: 20 B per particle and frame, 48 B per primitive and frame, allocated here for max_frames.
+ * ud_mpm_render_frames: x [M,n_particles,3], prim_pos [M,n_prims,3], prim_rot [M,n_prims,4] (both NULL when n_prims = 0), device
+ *   arrays.  Two launches (k_mr_setup, k_mr_tile), no allocation, no host synchronisation.  A null handle / x / color / depth
+ *   (prim_pos / prim_rot with n_prims > 0), M < 1 or M > max_frames: UD_ERR_INVALID, nothing launched, no output touched.  Results
+ *   are bit-identical from run to run.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct ud_mpm_render ud_mpm_render;
+/* (a tagged struct, as ud_cloth_render_conf) */
+typedef struct ud_mpm_render_conf {
+  int width;                  /* 640 */
+  int height;                 /* 480 */
+  double yfov;                /* pi / 3 */
+  double znear;               /* 0.05 */
+  double camera_pos[3];       /* (0.9, 0.5, 1.0), render frame; also the pose of both lights */
+  double camera_target[3];    /* (0.6, 0.5, 0.0) */
+  double camera_up[3];        /* (0, 0, 1) */
+  double ground_min[2];       /* (-0.02, -0.04) */
+  double ground_max[2];       /* (0.98, 0.96) */
+  double ground_z;            /* -0.02 */
+  float particle_color[4];    /* RGBA in [0, 1]; alpha is used in point mode only */
+  float prim_color[3];        /* base colours, RGB in [0, 1] */
+  float ground_color[3];
+  int mode;                   /* 0 spheres, 1 points */
+  double radius;              /* 0.008 (mode 0) */
+  int point_size;             /* 1 pixel (mode 1) */
+  int n_particles;            /* N of every call */
+  int n_prims;                /* primitives per frame, >= 0 */
+  int prim_kind;              /* 0 box, 1 cut hollow sphere */
+  int max_frames;             /* arenas are allocated for this many frames; a call with more returns UD_ERR_INVALID */
+} ud_mpm_render_conf;
+int ud_mpm_render_create(const ud_mpm_render_conf* conf, const float* prim_sizes, ud_mpm_render** out);
+int ud_mpm_render_destroy(ud_mpm_render* h);
+int ud_mpm_render_frames(ud_mpm_render* h, int M, const float* x, const float* prim_pos, const float* prim_rot, unsigned char* color,
+                         float* depth, int* id, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,7 @@ SYMBOLS = [
     "ud_plb_policy_n_params", "ud_plb_policy_tape_bytes", "ud_plb_policy_fwd", "ud_plb_policy_bwd",
     "ud_plb_render_create", "ud_plb_render_destroy", "ud_plb_render_set_light", "ud_plb_render_bake", "ud_plb_render_read_volume", "ud_plb_render_gbuffer", "ud_plb_render_image",
     "ud_cloth_render_create", "ud_cloth_render_destroy", "ud_cloth_render_frames",
+    "ud_mpm_render_create", "ud_mpm_render_destroy", "ud_mpm_render_frames",
     "ud_pc_fps", "ud_pc_ball_query", "ud_pc_group_fwd", "ud_pc_group_bwd",
     "ud_chamfer_fwd", "ud_chamfer_bwd", "ud_cloth_pnp_fwd", "ud_cloth_pnp_bwd", "ud_cloth_depth_fwd", "ud_cloth_depth_bwd",
     "ud_mpm_focus_fwd", "ud_mpm_focus_bwd", "ud_mpm_finish_fwd", "ud_mpm_finish_bwd",
@@ -86,6 +87,14 @@ class ud_cloth_render_conf(C.Structure):
                 ("camera_target", C.c_double * 3), ("camera_up", C.c_double * 3), ("ground_min", C.c_double * 2), ("ground_max", C.c_double * 2),
                 ("ground_z", C.c_double), ("cloth_color", C.c_float * 3), ("ground_color", C.c_float * 3), ("sphere_color", C.c_float * 3),
                 ("n_vertices", C.c_int), ("n_faces", C.c_int), ("n_spheres", C.c_int), ("max_frames", C.c_int)]
+
+
+class ud_mpm_render_conf(C.Structure):
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("yfov", C.c_double), ("znear", C.c_double), ("camera_pos", C.c_double * 3),
+                ("camera_target", C.c_double * 3), ("camera_up", C.c_double * 3), ("ground_min", C.c_double * 2), ("ground_max", C.c_double * 2),
+                ("ground_z", C.c_double), ("particle_color", C.c_float * 4), ("prim_color", C.c_float * 3), ("ground_color", C.c_float * 3),
+                ("mode", C.c_int), ("radius", C.c_double), ("point_size", C.c_int), ("n_particles", C.c_int), ("n_prims", C.c_int),
+                ("prim_kind", C.c_int), ("max_frames", C.c_int)]
 
 
 def build(force: bool = False) -> str:
@@ -154,6 +163,9 @@ def lib():
         L.ud_cloth_render_create.argtypes = [C.c_void_p] * 3
         L.ud_cloth_render_destroy.argtypes = [C.c_void_p]
         L.ud_cloth_render_frames.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6
+        L.ud_mpm_render_create.argtypes = [C.c_void_p] * 3
+        L.ud_mpm_render_destroy.argtypes = [C.c_void_p]
+        L.ud_mpm_render_frames.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 7
         L.ud_pc_fps.argtypes = [C.c_int] * 3 + [C.c_void_p] * 4
         L.ud_pc_ball_query.argtypes = [C.c_int] * 3 + [C.c_float, C.c_int] + [C.c_void_p] * 5
         L.ud_pc_group_fwd.argtypes = [C.c_int] * 5 + [C.c_void_p] * 6

@@ -6,7 +6,12 @@ Mirrors /root/reference/DaXBench/daxbench/core/envs/basic/mpm_env.py:
 The reference jit-compiles step_diff around lax.scan(simulator.step_jax); here each scanned `step` is one kernel
 launch (SimpleMPMSimulator.step_jax); the focus shift before it and un-shift / nan_to_num / reward / observation after it
 are one kernel each way (csrc/env_glue.hip), with the op-by-op torch form kept as `step_diff_unfused`.
-Rendering (pyrender / trimesh) is out of scope.
+    render / step_with_render :171-183, :200-236   (ParticlePyRenderer / WaterPyRenderer, core/engine/pyrender/py_render.py:120-174)
+Rendering is a particle and primitive rasteriser on the device (engine/mpm_render.py, csrc/mpm_render.hip): the reference's camera,
+sphere radius, particle colours and unmirrored RGB orientation.  Stated deviations (see engine/mpm_render.py): analytic spheres for the
+uv_sphere meshes, one-layer point blending, the primitives drawn from the simulator's own transform instead of the reference's
+Euler-angle detour, a sphere-traced bowl for its marching-cubes mesh, whole-particle drop at the near plane, this project's shading and
+colours, a flat ground.  The renderer handle is created by the first render call: an env that never renders allocates nothing for it.
 """
 from __future__ import annotations
 
@@ -242,11 +247,60 @@ class MPMEnv:
 
         return step_diff
 
-    def step_with_render(self, actions, state, visualize=True):
-        raise NotImplementedError("rendering (pyrender) is outside the hot path; see DESIGN.md")
+    # ------------------------------------------------------------------------------------------------
+    _render_defaults = {}      # the env's own MpmRenderConf fields (the pour envs: points in the water colour)
+    _render_stale = True       # set by every reset: the next render call reads the primitives' sizes back
+
+    def _render_conf(self):
+        from ...engine.mpm_render import MpmRenderConf
+        rc = getattr(self.conf, "render_conf", None)
+        if rc is None or isinstance(rc, dict):
+            return MpmRenderConf(**{**self._render_defaults, **(rc or {})})
+        return rc
+
+    def _renderer(self, state):
+        """the handle for this state's particle count, primitive sizes and SDF kind; created by the first render call, and again when
+        one of them has changed after a reset (the sizes are read back once per reset, not per call)"""
+        from ...engine.mpm_render import BOX, CONTAINER, MpmRenderer
+        r = getattr(self, "_mpm_renderer", None)
+        shape = (int(state.x.shape[-2]), len(state.primitives), CONTAINER if self.simulator.sdf_kind == "container" else BOX)
+        same_shape = r is not None and (r.n_particles, r.n_prims, r.prim_kind) == shape
+        if same_shape and not self._render_stale:
+            return r
+        sizes = np.zeros((0, 3), np.float32)
+        if state.primitives:
+            sizes = np.stack([p.size.detach().reshape(-1, 3)[0].cpu().numpy() for p in state.primitives]).astype(np.float32)
+        if not same_shape or not np.array_equal(r.prim_sizes, sizes):
+            r = MpmRenderer(shape[0], sizes, shape[2], self._render_conf(), device=self.device)
+        self._mpm_renderer, self._render_stale = r, False
+        return r
+
+    def render_batch(self, state, want_id=False):
+        """The camera view of every leading index of a state ([B]) or a state list ([T,B]), one call: device tensors (color u8
+        [..., 480, 640, 3] RGB, not mirrored, as the reference returns it; depth f32 [..., 480, 640]; with want_id the id image).  Each
+        primitive is drawn at position[..., 0, :] / rotation[..., 0, :] (mpm_env.py:205-206 of the reference)."""
+        x = state.x.detach()
+        r = self._renderer(state)
+        pos = rot = None
+        if state.primitives:
+            pos = torch.stack([p.position.detach()[..., 0, :] for p in state.primitives], -2)
+            rot = torch.stack([p.rotation.detach()[..., 0, :] for p in state.primitives], -2)
+        return r.frames(x, pos, rot, want_id=want_id)
 
     def render(self, state, visualize=False):
-        raise NotImplementedError("rendering (pyrender) is outside the hot path; see DESIGN.md")
+        """(color [480,640,3] u8 RGB, depth [480,640] f32) of env 0 as NumPy arrays (:185-193); `visualize` is accepted, there is no window."""
+        first = state._replace(x=state.x[:1], primitives=[p._replace(position=p.position[:1], rotation=p.rotation[:1]) for p in state.primitives])
+        color, depth = self.render_batch(first)
+        return color[0].cpu().numpy(), depth[0].cpu().numpy()
+
+    def step_with_render(self, actions, state, visualize=True):
+        """step_diff, plus info["img_list"]: the colour image of env 0 for every entry of info["state_list"], rendered in one call (:171-183)."""
+        obs, reward, done, info = self.step_diff(actions, state)
+        sl = info["state_list"]
+        first = sl._replace(x=sl.x[:, 0], primitives=[p._replace(position=p.position[:, 0], rotation=p.rotation[:, 0]) for p in sl.primitives])
+        color, _ = self.render_batch(first)
+        info["img_list"] = list(color.cpu().numpy())
+        return obs, reward, done, info
 
     def clean_up_b4_reset(self):
         self.state = None
@@ -254,6 +308,7 @@ class MPMEnv:
     def initialize_after_adding_particle_primitives(self, state):   # :195-198
         self.state = self.simulator.reset_jax(state)
         self.init_state = self.state
+        self._render_stale = True      # the renderer (if any) checks the primitives' sizes again on its next call
 
     def create_primitive(self, conf, state, friction, color, size, init_pos, softness=666):   # :207-217
         p_state = create_primitive(conf, friction=friction, softness=softness, color=color, size=np.array(size),

@@ -55,6 +55,8 @@ PourWaterConfig = DefaultConf
 
 
 class PourWaterEnv(MPMEnv):
+    # WaterPyRenderer (py_render.py:148-174): GL points of one pixel in (100, 100, 249, 125) / 255
+    _render_defaults = dict(mode=1, particle_color=(100 / 255, 100 / 255, 249 / 255, 125 / 255))
 
     def __init__(self, batch_size, seed, max_steps=100, conf=None, aux_reward=False, device="cuda", **kwargs):
         conf = DefaultConf() if conf is None else conf
