@@ -1253,6 +1253,11 @@ int ud_mpm_create(const ud_mpm_conf* conf, const int* material, const float* har
   const bool large = N > 128 || !conf->use_position_control || conf->deterministic;
   if (!large && S * 3 > 256) { ud::set_error("ud_mpm_create: steps=%d too large for the in-LDS primitive arrays", S); return UD_ERR_UNSUPPORTED; }
   if (conf->res[0] > 1024 || conf->res[1] > 1024 || conf->res[2] > 1024) { ud::set_error("ud_mpm_create: res > 1024"); return UD_ERR_UNSUPPORTED; }
+  // refused here, before anything is allocated: mpm_large_create reports a failure as "no handle", which reads as UD_ERR_HIP below
+  if (conf->deterministic && N > ud::LG_DET_MAX_PARTICLES) {
+    ud::set_error("ud_mpm_create: deterministic mode sorts an env's particles in one workgroup's LDS: n_particles <= %d", ud::LG_DET_MAX_PARTICLES);
+    return UD_ERR_UNSUPPORTED;
+  }
   auto* h = new ud_mpm();
   ud::MpmConst& c = h->c;
   c.N = N; c.Np = (N + 15) / 16 * 16; c.n_grid = conf->n_grid; c.steps = S;

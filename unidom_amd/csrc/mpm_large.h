@@ -5,6 +5,7 @@
 namespace ud {
 
 struct MpmLarge;
+constexpr int LG_DET_MAX_PARTICLES = 8192;   // deterministic mode: an env's particles are sorted in one workgroup's LDS (64 KB of 8-byte entries)
 // kernel selection of a handle, fixed at create (ud_mpm_conf: max_envs and the `tune_*` fields; 0 = the library's choice by measurement)
 struct LgTune {
   int max_envs;            // every arena is sized for this many envs at create

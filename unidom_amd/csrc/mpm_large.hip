@@ -924,6 +924,7 @@ __device__ __forceinline__ unsigned morton10(unsigned v) {   // spread the low 1
   return v;
 }
 constexpr int LG_SORT_MAX = 8192;   // particles per env the LDS sort holds (64 KB of 8-byte entries)
+static_assert(LG_DET_MAX_PARTICLES == LG_SORT_MAX, "ud_mpm_create (mpm.hip) refuses a deterministic handle by the same number");
 __global__ void __launch_bounds__(1024) lg_sort(MpmConst c, int b0, const float* x, int* perm, long perm_stride, int npow2) {
   extern __shared__ unsigned long long lg_sk[];
   const int b = blockIdx.x + b0, tid = threadIdx.x;
