@@ -519,7 +519,9 @@ int ud_plb_loss_bwd_gap(ud_plb* h, int B, const double* x, const double* prim_po
 /* Grid mass of a particle state, the field a goal is made of (TaichiEnv.get_grid_mass; create_goal1.py saves it as the target
  * density): grid_mass [B, n_grid^3] = the loss's p2g of the particle masses, written into the caller's array (zeroed here, summed with
  * atomics).  Any handle kind and path; B is not bound by max_envs: the call reads the handle's constants only and touches none of its
- * arenas, so it may run next to a loss call of the same handle on another stream. */
+ * arenas, so it may run next to a loss call of the same handle on another stream.  Per axis base = (int)(x inv_dx - 0.5), truncated
+ * toward zero, and each of the three stencil indices is clamped on its own, min(max(base + o, 0), n_grid - 1): a particle near or
+ * outside a wall adds several of its 27 terms to one wall cell, and the total mass is N p_mass wherever the particles are. */
 int ud_plb_grid_mass(ud_plb* h, int B, const double* x, double* grid_mass, void* stream);
 
 /* Target SDF of T target densities (Loss.update_target / update_target_sdf, engine/losses/loss.py:77-106), handle-free: launches only,
@@ -563,7 +565,9 @@ int ud_plb_density_iou(long G, int T, const double* a, const double* b, int b_ba
  * UD_ERR_INVALID.  ud_plb_density_seq_work_bytes(h, M) = 8 G min(M, C) with C = the items that fit into 256 MiB (at least one, at
  * most 65535): never more than max(256 MiB, 8 G).
  * sign (may be NULL = no backward): ud_plb_density_seq_sign_bytes(h, M) bytes (2 bits per cell and item, 16-byte aligned), opaque;
- * three-valued, 0 where df == 0, as ud_plb_loss_bwd decides it (an empty cell of an empty target sends nothing).
+ * three-valued, 0 where df == 0 and where df is NaN, as ud_plb_loss_bwd decides it (an empty cell of an empty target sends nothing).
+ * A NaN in a target cell or in a coordinate makes the loss of the items that read it NaN and leaves every other item's loss, sign
+ * field and g_x as they are without it; the backward reads the sign bit of the CLAMPED cell, the one the forward added to.
  * A target_index[m] outside [0, T) reads nothing out of bounds: loss[m] = NaN, that item's sign field is all zero, so its g_x is 0.
  * ud_plb_density_seq_bwd: g_x[m,p] = inv_dx g_loss[m] p_mass sum_{27 cells} sign_I grad w_I -- one gather per particle, no atomics, no
  * scratch: bit-identical from run to run for one sign field.  x is the forward's.
@@ -578,9 +582,10 @@ int ud_plb_density_seq_bwd(ud_plb* h, long M, const double* x, const void* sign,
  * a [M,Na,3]; b [Tb,Nb,3]; b_index [M] (device int32; NULL = cloud 0 for every item); out [M]:
  *   out = mean_i min_j d(a_i, b_j) + mean_j min_i d(a_i, b_j),  d = sqrt((dx dx + dy dy) + dz dz), unfused.
  * min_ab [M,Na], min_ba [M,Nb] (each may be NULL) receive the two sets of minima.  NaN propagates as np.min does.  The means are
- * fixed-order sums: the same input gives the same bits, with or without the min arrays.  With both arrays given the minima are taken
- * by ceil(Na / 256) + ceil(Nb / 256) workgroups per item (the design point, 10 000 x 10 000 points per item); otherwise by one
- * workgroup per item.  Nothing of size Na x Nb is ever stored.  A b_index[m] outside [0, Tb) reads nothing out of bounds: out[m] and
+ * fixed-order sums: the same input gives the same bits, with or without the min arrays.  With both arrays given and M <= 65535 the
+ * minima are taken by ceil(Na / 256) + ceil(Nb / 256) workgroups per item (the design point, 10 000 x 10 000 points per item);
+ * with one array or none, or M > 65535, by one workgroup per item, which fills whichever array is given.  Every route gives the same
+ * bits in out and in the minima.  Nothing of size Na x Nb is ever stored.  A b_index[m] outside [0, Tb) reads nothing out of bounds: out[m] and
  * that item's minima are NaN.  M, Na, Nb, Tb < 1 or a null a / b / out: UD_ERR_INVALID. */
 int ud_plb_chamfer(long M, int Na, const double* a, int Tb, int Nb, const double* b, const int* b_index, double* out, double* min_ab,
                    double* min_ba, void* stream);
