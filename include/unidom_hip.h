@@ -809,7 +809,7 @@ int ud_mpm_finish_bwd(int B, int N, int n_prim, int S, int Q, const float* x, co
  * ------------------------------------------------------------------------------------------------ */
 #define UD_PLB_RENDER_MAX_PRIM 4
 typedef struct ud_plb_render ud_plb_render;
-/* (a tagged struct: the generated binding stub of INTEGRATION.md lists the three simulator confs) */
+/* (the tag is not needed: the binding parses tagged and untagged structs alike, and tools/gen_binding_stub.py names the structs it lists) */
 typedef struct ud_plb_render_conf {
   double dx;                  /* cfg.RENDERER.dx, default 1 / 150 */
   int voxel_res[3];           /* (168, 168, 168); each >= 2 * bake_size and in [2, 1024], else UD_ERR_INVALID */
@@ -907,7 +907,6 @@ int ud_plb_render_image(ud_plb_render* h, int B, const double* prim_pos, const d
  *   or M > max_frames: UD_ERR_INVALID, nothing launched, no output touched.  Results are bit-identical from run to run.
  * ------------------------------------------------------------------------------------------------ */
 typedef struct ud_cloth_render ud_cloth_render;
-/* (a tagged struct: the generated binding stub of INTEGRATION.md lists the three simulator confs) */
 typedef struct ud_cloth_render_conf {
   int width;                  /* 640 */
   int height;                 /* 480 */
@@ -1003,7 +1002,6 @@ int ud_cloth_render_frames(ud_cloth_render* h, int M, const float* vertices, con
  *   are bit-identical from run to run.
  * ------------------------------------------------------------------------------------------------ */
 typedef struct ud_mpm_render ud_mpm_render;
-/* (a tagged struct, as ud_cloth_render_conf) */
 typedef struct ud_mpm_render_conf {
   int width;                  /* 640 */
   int height;                 /* 480 */

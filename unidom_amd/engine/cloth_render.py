@@ -40,10 +40,6 @@ class ClothRenderConf:
             setattr(self, k, v)
 
 
-def _p(t):
-    return C.c_void_p(0) if t is None else C.c_void_p(t.data_ptr())
-
-
 class ClothRenderer:
     """frames(x_grid, primitive0) -> (color u8 [..., H, W, 3], depth f32 [..., H, W][, tri i32 [..., H, W]]) on the device, for any leading
     shape; more than max_frames frames are rendered in chunks of max_frames.  `sim`: a ClothSimulator (its N and indices)."""
@@ -84,11 +80,12 @@ class ClothRenderer:
         color = torch.empty((M, H, W, 3), dtype=torch.uint8, device=self.device)
         depth = torch.empty((M, H, W), dtype=torch.float32, device=self.device)
         tri = torch.empty((M, H, W), dtype=torch.int32, device=self.device) if want_tri else None
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        stream = _lib.stream(self.device)
         L = _lib.lib()
         for m0 in range(0, M, self.max_frames):
             m1 = min(M, m0 + self.max_frames)
-            _lib.check(L.ud_cloth_render_frames(self._h, m1 - m0, _p(x[m0:m1]), _p(sp[m0:m1]) if S > 0 else _p(None), _p(color[m0:m1]),
-                                                _p(depth[m0:m1]), _p(tri[m0:m1]) if want_tri else _p(None), stream), "ud_cloth_render_frames")
+            _lib.check(L.ud_cloth_render_frames(self._h, m1 - m0, _lib.ptr(x[m0:m1]), _lib.ptr(sp[m0:m1] if S > 0 else None),
+                                                _lib.ptr(color[m0:m1]), _lib.ptr(depth[m0:m1]), _lib.ptr(tri[m0:m1] if want_tri else None),
+                                                stream), "ud_cloth_render_frames")
         out = (color.reshape(lead + (H, W, 3)), depth.reshape(lead + (H, W)))
         return out + (tri.reshape(lead + (H, W)),) if want_tri else out

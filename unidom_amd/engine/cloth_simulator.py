@@ -63,13 +63,13 @@ class _Rollout(torch.autograd.Function):
         need_grad = any(ctx.needs_input_grad)  # all False under torch.no_grad()
         ckpt = None
         if need_grad:
-            nbytes = L.ud_cloth_ckpt_bytes(sim._h, C.c_int(B), C.c_int(T))
+            nbytes = L.ud_cloth_ckpt_bytes(sim._h, B, T)
             ckpt = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev)
         grasp = torch.zeros((T, sim.substeps, B, 2, P), dtype=torch.uint8, device=dev) if sim.record_grasp else None
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _lib.stream(dev)
         ev = sim._prof_begin("fwd")
         _lib.check(L.ud_cloth_rollout_fwd(
-            sim._h, C.c_int(B), C.c_int(T), _lib.ptr(x), _lib.ptr(v), _lib.ptr(prim), _lib.ptr(stiffness),
+            sim._h, B, T, _lib.ptr(x), _lib.ptr(v), _lib.ptr(prim), _lib.ptr(stiffness),
             _lib.ptr(mu), _lib.ptr(actions), _lib.ptr(xo), _lib.ptr(vo), _lib.ptr(po), _lib.ptr(xl),
             _lib.ptr(vl), _lib.ptr(pl), _lib.ptr(ckpt), _lib.ptr(grasp), stream), "ud_cloth_rollout_fwd")
         sim._prof_end(ev)
@@ -95,12 +95,12 @@ class _Rollout(torch.autograd.Function):
         gx0, gv0, gp0 = torch.empty_like(gx), torch.empty_like(gv), torch.empty_like(gp)
         ga = torch.empty((T, B, 8), device=dev)
         gk, gmu = torch.empty((B,), device=dev), torch.empty((B,), device=dev)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _lib.stream(dev)
         ev = sim._prof_begin("bwd")
         _lib.check(L.ud_cloth_rollout_bwd(
-            sim._h, C.c_int(B), C.c_int(T), _lib.ptr(ckpt), _lib.ptr(stiffness), _lib.ptr(mu), _lib.ptr(actions),
+            sim._h, B, T, _lib.ptr(ckpt), _lib.ptr(stiffness), _lib.ptr(mu), _lib.ptr(actions),
             _lib.ptr(gx), _lib.ptr(gv), _lib.ptr(gp), _lib.ptr(gxl), _lib.ptr(gvl), _lib.ptr(gpl),
-            C.c_int(1 if sim.normalize_grad else 0), _lib.ptr(gx0), _lib.ptr(gv0), _lib.ptr(gp0), _lib.ptr(ga),
+            1 if sim.normalize_grad else 0, _lib.ptr(gx0), _lib.ptr(gv0), _lib.ptr(gp0), _lib.ptr(ga),
             _lib.ptr(gk), _lib.ptr(gmu), stream), "ud_cloth_rollout_bwd")
         sim._prof_end(ev)
         return None, gx0, gv0, gp0, gk, gmu, ga, None
@@ -196,14 +196,14 @@ class ClothSimulator:
         """Device-side failure flags of this handle (include/unidom_hip.h: ud_cloth_poll_timeouts): a part of the
         several-workgroup kernels that gave up waiting for a sibling.  Synchronises the current stream; raises UnidomError.
         apg.train calls it once per iteration (the update has synchronised by then); one-workgroup bodies return at once."""
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        stream = _lib.stream(self.device)
         n = _lib.lib().ud_cloth_poll_timeouts(self._h, stream)
         if n != 0:
             raise _lib.UnidomError(f"cloth kernels (status {n}): {_lib.lib().ud_last_error().decode()}")
 
     def launch_envs(self, B=None):
         """envs per kernel launch of a call with B envs (ud_cloth_launch_envs)"""
-        return int(_lib.lib().ud_cloth_launch_envs(self._h, C.c_int(self.batch_size if B is None else B)))
+        return int(_lib.lib().ud_cloth_launch_envs(self._h, self.batch_size if B is None else B))
 
     @property
     def several_workgroups(self):

@@ -42,10 +42,6 @@ class MpmRenderConf(ClothRenderConf):
             setattr(self, k, v)
 
 
-def _p(t):
-    return C.c_void_p(0) if t is None else C.c_void_p(t.data_ptr())
-
-
 class MpmRenderer:
     """frames(x, prim_pos, prim_rot) -> (color u8 [..., H, W, 3] RGB, depth f32 [..., H, W][, id i32 [..., H, W]]) on the device, for any
     leading shape; more than max_frames frames are rendered in chunks of max_frames.  prim_sizes [n_prims, 3]: half sizes (box) or
@@ -93,13 +89,13 @@ class MpmRenderer:
         color = torch.empty((M, H, W, 3), dtype=torch.uint8, device=self.device)
         depth = torch.empty((M, H, W), dtype=torch.float32, device=self.device)
         ids = torch.empty((M, H, W), dtype=torch.int32, device=self.device) if want_id else None
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        stream = _lib.stream(self.device)
         L = _lib.lib()
         with torch.cuda.device(self.device):
             for m0 in range(0, M, self.max_frames):
                 m1 = min(M, m0 + self.max_frames)
-                _lib.check(L.ud_mpm_render_frames(self._h, m1 - m0, _p(x[m0:m1]), _p(pp[m0:m1]) if NP else _p(None),
-                                                  _p(pr[m0:m1]) if NP else _p(None), _p(color[m0:m1]), _p(depth[m0:m1]),
-                                                  _p(ids[m0:m1]) if want_id else _p(None), stream), "ud_mpm_render_frames")
+                _lib.check(L.ud_mpm_render_frames(self._h, m1 - m0, _lib.ptr(x[m0:m1]), _lib.ptr(pp[m0:m1] if NP else None),
+                                                  _lib.ptr(pr[m0:m1] if NP else None), _lib.ptr(color[m0:m1]), _lib.ptr(depth[m0:m1]),
+                                                  _lib.ptr(ids[m0:m1] if want_id else None), stream), "ud_mpm_render_frames")
         out = (color.reshape(lead + (H, W, 3)), depth.reshape(lead + (H, W)))
         return out + (ids.reshape(lead + (H, W)),) if want_id else out

@@ -61,12 +61,12 @@ class _Step(torch.autograd.Function):
         pvo, pwo = torch.empty_like(ppos), torch.empty_like(ppos)
         ckpt = None
         if any(ctx.needs_input_grad):
-            ckpt = torch.empty((L.ud_mpm_ckpt_bytes(sim._h, C.c_int(B)) // 4,), dtype=torch.float32, device=dev)
+            ckpt = torch.empty((L.ud_mpm_ckpt_bytes(sim._h, B) // 4,), dtype=torch.float32, device=dev)
         status = torch.empty((B,), dtype=torch.int32, device=dev)   # every entry is written by the call (include/unidom_hip.h)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _lib.stream(dev)
         ev = sim._prof_begin("fwd")
         _lib.check(L.ud_mpm_step_fwd(
-            sim._h, C.c_int(B), *[_lib.ptr(t) for t in (x, v, Cm, F, J, ppos, prot, psize, friction, mu, lamda, action)],
+            sim._h, B, *[_lib.ptr(t) for t in (x, v, Cm, F, J, ppos, prot, psize, friction, mu, lamda, action)],
             *[_lib.ptr(t) for t in (xo, vo, Co, Fo, Jo, ppo, pro, pvo, pwo)], _lib.ptr(ckpt), _lib.ptr(status), stream),
             "ud_mpm_step_fwd")
         sim._prof_end(ev)
@@ -109,12 +109,12 @@ class _Step(torch.autograd.Function):
         ofr, omu, ola = (torch.empty((B,), device=dev) for _ in range(3))
         oa = torch.empty((B, 6 * sim.n_primitive), device=dev)
         status = torch.empty((B,), dtype=torch.int32, device=dev)   # every entry is written by the call (include/unidom_hip.h)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _lib.stream(dev)
         ev = sim._prof_begin("bwd")
         clip = (1 if sim.clip_grad else 0) | (4 if ctx.handoff else (2 if sim._overflowed(ctx.overflow) else 0))
         _lib.check(L.ud_mpm_step_bwd(
-            sim._h, C.c_int(B), _lib.ptr(ckpt), *[_lib.ptr(t) for t in (psize, friction, mu, lamda, action)],
-            *[_lib.ptr(t) for t in (gx, gv, gC, gF, gppos, gprot)], C.c_int(clip),
+            sim._h, B, _lib.ptr(ckpt), *[_lib.ptr(t) for t in (psize, friction, mu, lamda, action)],
+            *[_lib.ptr(t) for t in (gx, gv, gC, gF, gppos, gprot)], clip,
             *[_lib.ptr(t) for t in (ox, ov, oC, oF, opp, opr, ofr, omu, ola, oa)], _lib.ptr(status), stream), "ud_mpm_step_bwd")
         sim._prof_end(ev)
         if ctx.handoff:                        # value 8 = "this env's grid was recomputed": counted on the device, not an error
@@ -331,7 +331,7 @@ class SimpleMPMSimulator:
         """A part that gave up waiting (bit 4) skipped the zeroing of its cells: the handle's arenas go back to their rest state
         (ud_mpm_reset, asynchronous on the current stream) before anything else runs on it."""
         if bool((flags & 4).any()):
-            stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            stream = _lib.stream(self.device)
             _lib.check(_lib.lib().ud_mpm_reset(self._h, stream), "ud_mpm_reset")
 
     def _prof_begin(self, kind):
@@ -353,13 +353,13 @@ class SimpleMPMSimulator:
             return 0.0
         ckpt, B = self._last_ckpt
         cells = torch.empty((B,), dtype=torch.int32, device=ckpt.device)
-        stream = C.c_void_p(torch.cuda.current_stream(ckpt.device).cuda_stream)
-        _lib.check(_lib.lib().ud_mpm_ckpt_cells(self._h, C.c_int(B), _lib.ptr(ckpt), _lib.ptr(cells), stream), "ud_mpm_ckpt_cells")
+        stream = _lib.stream(ckpt.device)
+        _lib.check(_lib.lib().ud_mpm_ckpt_cells(self._h, B, _lib.ptr(ckpt), _lib.ptr(cells), stream), "ud_mpm_ckpt_cells")
         return float(cells.double().mean().item()) / float(self.conf.steps)
 
     def launch_plan(self, B):
         """ud_mpm_launch_plan: 0 = one workgroup per env; bit 0 many-workgroup path, bit 1 persistent forward, bit 2 two-launch backward"""
-        return int(_lib.lib().ud_mpm_launch_plan(self._h, C.c_int(B)))
+        return int(_lib.lib().ud_mpm_launch_plan(self._h, B))
 
     def check_status(self):
         """Host sync: raise if any launch since the last check overflowed its LDS cell table."""
@@ -376,7 +376,7 @@ class SimpleMPMSimulator:
             bad = self._status_acc.item()
             self._status_acc = None
             if bad and self._h_large:      # which bit it was is gone in the fold: a reset is cheap and always right
-                stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+                stream = _lib.stream(self.device)
                 _lib.check(_lib.lib().ud_mpm_reset(self._h, stream), "ud_mpm_reset")
             if bad:
                 raise _lib.UnidomError("MPM device-side capacity exceeded (UD_ERR_OVERFLOW): LDS cell table (one-workgroup path) or "

@@ -9,20 +9,10 @@ One target is shared by all envs, as ud_plb_loss_* takes it.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 import torch
 
 from .. import _lib
-
-
-def _p(t):
-    return C.c_void_p(0) if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def target_sdf(density, threshold=1e-4, sweeps=0, want_nearest=False):
@@ -39,8 +29,8 @@ def target_sdf(density, threshold=1e-4, sweeps=0, want_nearest=False):
     run = torch.empty((T,), dtype=torch.int32, device=d.device)
     nbytes = L.ud_plb_target_work_bytes(n, T)
     work = torch.empty((max(int(nbytes), 4) // 4,), dtype=torch.int32, device=d.device)
-    _lib.check(L.ud_plb_target_sdf(n, T, _p(d), float(threshold), int(sweeps), _p(sdf), _p(nearest), _p(run), _p(work), _stream(d.device)),
-               "ud_plb_target_sdf")
+    _lib.check(L.ud_plb_target_sdf(n, T, _lib.ptr(d), float(threshold), int(sweeps), *[_lib.ptr(t) for t in (sdf, nearest, run, work)],
+                                   _lib.stream(d.device)), "ud_plb_target_sdf")
     return sdf, nearest, run
 
 
@@ -56,7 +46,8 @@ def density_iou(a, b):
     assert batched or b.numel() == G, (tuple(a.shape), tuple(b.shape))
     out = torch.empty((T,), dtype=torch.float64, device=a.device)
     work = torch.empty((int(L.ud_plb_density_iou_work_bytes(T)) // 8,), dtype=torch.float64, device=a.device)
-    _lib.check(L.ud_plb_density_iou(G, T, _p(a), _p(b), int(batched), _p(out), _p(work), _stream(a.device)), "ud_plb_density_iou")
+    _lib.check(L.ud_plb_density_iou(G, T, _lib.ptr(a), _lib.ptr(b), int(batched), _lib.ptr(out), _lib.ptr(work), _lib.stream(a.device)),
+               "ud_plb_density_iou")
     return out
 
 

@@ -31,10 +31,6 @@ def policy_dims(n_particles, n_primitive, action_dim, hidden_dims, n_observed_pa
     return obs_step, obs_num, (obs_num * 6 + 7 * n_primitive,) + tuple(int(h) for h in hidden_dims) + (int(action_dim),)
 
 
-def _p(t):
-    return C.c_void_p(0) if t is None else C.c_void_p(t.data_ptr())
-
-
 def _c(t):
     return t.detach().to(torch.float64).contiguous()
 
@@ -51,9 +47,9 @@ class _PlbPolicyAct(torch.autograd.Function):
         tape = None
         if any(ctx.needs_input_grad):
             tape = torch.empty((L.ud_plb_policy_tape_bytes(B, policy.n_layer, policy._cdims) // 8,), dtype=torch.float64, device=x.device)
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        _lib.check(L.ud_plb_policy_fwd(*policy._shape_args(B), _p(x), _p(v), _p(pp), _p(pr), _p(params), policy._param_stride, _p(action),
-                                       _p(tape), stream), "ud_plb_policy_fwd")
+        stream = _lib.stream(x.device)
+        _lib.check(L.ud_plb_policy_fwd(*policy._shape_args(B), *[_lib.ptr(t) for t in (x, v, pp, pr, params)], policy._param_stride,
+                                       _lib.ptr(action), _lib.ptr(tape), stream), "ud_plb_policy_fwd")
         ctx.policy, ctx.B, ctx.shape_args = policy, B, policy._shape_args(B)
         ctx.save_for_backward(tape, params)
         return action
@@ -68,9 +64,9 @@ class _PlbPolicyAct(torch.autograd.Function):
         sim, dev = policy.sim, params.device
         mk = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
         gx, gv, gpp, gpr = mk(B, sim.n_particles, 3), mk(B, sim.n_particles, 3), mk(B, sim.n_primitive, 3), mk(B, sim.n_primitive, 4)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(L.ud_plb_policy_bwd(*ctx.shape_args, _p(params), policy._param_stride, _p(tape), _p(_c(g_action)), _p(gx), _p(gv), _p(gpp),
-                                       _p(gpr), _p(policy._grad), stream), "ud_plb_policy_bwd")
+        stream = _lib.stream(dev)
+        _lib.check(L.ud_plb_policy_bwd(*ctx.shape_args, _lib.ptr(params), policy._param_stride, _lib.ptr(tape), _lib.ptr(_c(g_action)),
+                                       *[_lib.ptr(t) for t in (gx, gv, gpp, gpr, policy._grad)], stream), "ud_plb_policy_bwd")
         return None, gx, gv, gpp, gpr, None
 
 

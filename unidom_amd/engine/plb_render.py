@@ -45,10 +45,6 @@ def render_conf_of(sim_conf, **overrides):
     return RenderConf(**kw)
 
 
-def _p(t):
-    return C.c_void_p(0) if t is None else C.c_void_p(t.data_ptr())
-
-
 class PlbRenderer:
     """bake(state, color) -> (bbox [B,2,3], status [B]); gbuffer(state) -> dict; render(state) -> image.  `state`: a PlbState, or anything with
     x [B,N,3], prim_pos [B,P,3] and optionally prim_rot [B,P,4] / prim_gap [B,P].  A state without prim_rot (no rot_state) is drawn with the
@@ -99,9 +95,6 @@ class PlbRenderer:
         except Exception:
             pass
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def bake(self, state, color=None):
         """set_particles: bake the envs' particle SDF volumes into the handle.  color: [N] int32 0xRRGGBB (None = the conf's).  Returns
         (bbox [B,2,3] f32, status [B] i32) without synchronising; status 1 = the cloud does not fit voxel_res (render() raises)."""
@@ -114,7 +107,8 @@ class PlbRenderer:
         assert col.numel() == self.n_particles
         bbox = torch.empty((B, 2, 3), dtype=torch.float32, device=self.device)
         status = torch.empty((B,), dtype=torch.int32, device=self.device)
-        _lib.check(_lib.lib().ud_plb_render_bake(self._h, B, _p(x), _p(col), _p(bbox), _p(status), self._stream()), "ud_plb_render_bake")
+        _lib.check(_lib.lib().ud_plb_render_bake(self._h, B, *[_lib.ptr(t) for t in (x, col, bbox, status)], _lib.stream(self.device)),
+                   "ud_plb_render_bake")
         return bbox, status
 
     def volume(self, B):
@@ -122,7 +116,7 @@ class PlbRenderer:
         r = tuple(self.conf.voxel_res)
         vol = torch.empty((B,) + r, dtype=torch.int64, device=self.device)
         sdf = torch.empty((B,) + r, dtype=torch.float32, device=self.device)
-        _lib.check(_lib.lib().ud_plb_render_read_volume(self._h, B, _p(vol), _p(sdf), self._stream()), "ud_plb_render_read_volume")
+        _lib.check(_lib.lib().ud_plb_render_read_volume(self._h, B, _lib.ptr(vol), _lib.ptr(sdf), _lib.stream(self.device)), "ud_plb_render_read_volume")
         return vol, sdf
 
     def _prims(self, state):
@@ -144,8 +138,8 @@ class PlbRenderer:
         t = torch.empty((B, W, H), dtype=torch.float32, device=self.device)
         normal = torch.empty((B, W, H, 3), dtype=torch.float32, device=self.device)
         albedo = torch.empty((B, W, H, 3), dtype=torch.float32, device=self.device)
-        _lib.check(_lib.lib().ud_plb_render_gbuffer(self._h, B, _p(pp), _p(pr), _p(pg), _p(kind), _p(t), _p(normal), _p(albedo), self._stream()),
-                   "ud_plb_render_gbuffer")
+        _lib.check(_lib.lib().ud_plb_render_gbuffer(self._h, B, *[_lib.ptr(a) for a in (pp, pr, pg, kind, t, normal, albedo)],
+                                                    _lib.stream(self.device)), "ud_plb_render_gbuffer")
         return dict(kind=kind, t=t, normal=normal, albedo=albedo)
 
     def image(self, state, spp=None, seed=0):
@@ -154,8 +148,8 @@ class PlbRenderer:
         W, H = self.conf.image_res
         pp, pr, pg = self._prims(state)
         img = torch.empty((B, H, W, 3), dtype=torch.float32, device=self.device)
-        _lib.check(_lib.lib().ud_plb_render_image(self._h, B, _p(pp), _p(pr), _p(pg), int(self.conf.spp if spp is None else spp), int(seed) & 0xFFFFFFFF,
-                                                  _p(img), self._stream()), "ud_plb_render_image")
+        _lib.check(_lib.lib().ud_plb_render_image(self._h, B, _lib.ptr(pp), _lib.ptr(pr), _lib.ptr(pg), int(self.conf.spp if spp is None else spp),
+                                                  int(seed) & 0xFFFFFFFF, _lib.ptr(img), _lib.stream(self.device)), "ud_plb_render_image")
         return img
 
     def render(self, state, spp=None, seed=0, mode="rgb_array", color=None, strict=True):

@@ -218,10 +218,6 @@ class ChopsticksConf(PlbConf):
     upper_bound = (1.0, 1.0, 1.0)
 
 
-def _p(t):
-    return C.c_void_p(0) if t is None else C.c_void_p(t.data_ptr())
-
-
 def _c(t):
     return t.detach().to(torch.float64).contiguous()
 
@@ -235,11 +231,11 @@ class _PlbStep(torch.autograd.Function):
         xo, vo, Co, Fo, po = (torch.empty_like(t) for t in (x, v, Cm, F, pp))
         ckpt = None
         if any(ctx.needs_input_grad):
-            ckpt = torch.empty((L.ud_plb_ckpt_bytes(sim._h, C.c_int(B)) // 8,), dtype=torch.float64, device=x.device)
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+            ckpt = torch.empty((L.ud_plb_ckpt_bytes(sim._h, B) // 8,), dtype=torch.float64, device=x.device)
+        stream = _lib.stream(x.device)
         ev = sim._prof_begin("fwd")
-        _lib.check(L.ud_plb_step_fwd(sim._h, C.c_int(B), _p(x), _p(v), _p(Cm), _p(F), _p(pp), _p(so), _p(action), _p(E), _p(nu),
-                                     _p(ys), _p(xo), _p(vo), _p(Co), _p(Fo), _p(po), _p(ckpt), stream), "ud_plb_step_fwd")
+        args = (x, v, Cm, F, pp, so, action, E, nu, ys, xo, vo, Co, Fo, po, ckpt)
+        _lib.check(L.ud_plb_step_fwd(sim._h, B, *[_lib.ptr(t) for t in args], stream), "ud_plb_step_fwd")
         sim._prof_end(ev)
         ctx.sim, ctx.B = sim, B
         ctx.save_for_backward(ckpt, so, action, E, nu, ys)
@@ -258,11 +254,10 @@ class _PlbStep(torch.autograd.Function):
         mk = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
         ox, ov, oC, oF, op, oa = mk(B, N, 3), mk(B, N, 3), mk(B, N, 3, 3), mk(B, N, 3, 3), mk(B, P, 3), mk(B, 3)
         oE, onu, oys, ofr = mk(B), mk(B), mk(B), mk(B)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _lib.stream(dev)
         ev = sim._prof_begin("bwd")
-        _lib.check(L.ud_plb_step_bwd(sim._h, C.c_int(B), _p(ckpt), _p(so), _p(action), _p(E), _p(nu), _p(ys), _p(gx), _p(gv), _p(gC),
-                                     _p(gF), _p(gpp), _p(ox), _p(ov), _p(oC), _p(oF), _p(op), _p(oa), _p(oE), _p(onu), _p(oys), _p(ofr),
-                                     stream), "ud_plb_step_bwd")
+        args = (ckpt, so, action, E, nu, ys, gx, gv, gC, gF, gpp, ox, ov, oC, oF, op, oa, oE, onu, oys, ofr)
+        _lib.check(L.ud_plb_step_bwd(sim._h, B, *[_lib.ptr(t) for t in args], stream), "ud_plb_step_bwd")
         sim._prof_end(ev)
         sim.ground_friction_grad = ofr if sim.ground_friction_grad is None else sim.ground_friction_grad + ofr
         return None, ox, ov, oC, oF, op, None, oa, oE, onu, oys
@@ -278,11 +273,11 @@ class _PlbStepRot(torch.autograd.Function):
         xo, vo, Co, Fo, po, ro = (torch.empty_like(t) for t in (x, v, Cm, F, pp, pr))
         ckpt = None
         if any(ctx.needs_input_grad):
-            ckpt = torch.empty((L.ud_plb_ckpt_bytes(sim._h, C.c_int(B)) // 8,), dtype=torch.float64, device=x.device)
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+            ckpt = torch.empty((L.ud_plb_ckpt_bytes(sim._h, B) // 8,), dtype=torch.float64, device=x.device)
+        stream = _lib.stream(x.device)
         ev = sim._prof_begin("fwd")
-        _lib.check(L.ud_plb_step_fwd_rot(sim._h, C.c_int(B), _p(x), _p(v), _p(Cm), _p(F), _p(pp), _p(pr), _p(so), _p(action), _p(E), _p(nu),
-                                         _p(ys), _p(xo), _p(vo), _p(Co), _p(Fo), _p(po), _p(ro), _p(ckpt), stream), "ud_plb_step_fwd_rot")
+        args = (x, v, Cm, F, pp, pr, so, action, E, nu, ys, xo, vo, Co, Fo, po, ro, ckpt)
+        _lib.check(L.ud_plb_step_fwd_rot(sim._h, B, *[_lib.ptr(t) for t in args], stream), "ud_plb_step_fwd_rot")
         sim._prof_end(ev)
         ctx.sim, ctx.B = sim, B
         ctx.save_for_backward(ckpt, so, action, E, nu, ys)
@@ -301,11 +296,10 @@ class _PlbStepRot(torch.autograd.Function):
         mk = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
         ox, ov, oC, oF, op, orot, oa = mk(B, N, 3), mk(B, N, 3), mk(B, N, 3, 3), mk(B, N, 3, 3), mk(B, P, 3), mk(B, P, 4), mk(B, sim.action_dim)
         oE, onu, oys, ofr = mk(B), mk(B), mk(B), mk(B)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _lib.stream(dev)
         ev = sim._prof_begin("bwd")
-        _lib.check(L.ud_plb_step_bwd_rot(sim._h, C.c_int(B), _p(ckpt), _p(so), _p(action), _p(E), _p(nu), _p(ys), _p(gx), _p(gv), _p(gC),
-                                         _p(gF), _p(gpp), _p(gpr), _p(ox), _p(ov), _p(oC), _p(oF), _p(op), _p(orot), _p(oa), _p(oE), _p(onu),
-                                         _p(oys), _p(ofr), stream), "ud_plb_step_bwd_rot")
+        args = (ckpt, so, action, E, nu, ys, gx, gv, gC, gF, gpp, gpr, ox, ov, oC, oF, op, orot, oa, oE, onu, oys, ofr)
+        _lib.check(L.ud_plb_step_bwd_rot(sim._h, B, *[_lib.ptr(t) for t in args], stream), "ud_plb_step_bwd_rot")
         sim._prof_end(ev)
         sim.ground_friction_grad = ofr if sim.ground_friction_grad is None else sim.ground_friction_grad + ofr
         return None, ox, ov, oC, oF, op, orot, None, oa, oE, onu, oys
@@ -321,11 +315,11 @@ class _PlbStepGap(torch.autograd.Function):
         xo, vo, Co, Fo, po, ro, go = (torch.empty_like(t) for t in (x, v, Cm, F, pp, pr, pg))
         ckpt = None
         if any(ctx.needs_input_grad):
-            ckpt = torch.empty((L.ud_plb_ckpt_bytes(sim._h, C.c_int(B)) // 8,), dtype=torch.float64, device=x.device)
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+            ckpt = torch.empty((L.ud_plb_ckpt_bytes(sim._h, B) // 8,), dtype=torch.float64, device=x.device)
+        stream = _lib.stream(x.device)
         ev = sim._prof_begin("fwd")
-        _lib.check(L.ud_plb_step_fwd_gap(sim._h, C.c_int(B), _p(x), _p(v), _p(Cm), _p(F), _p(pp), _p(pr), _p(pg), _p(so), _p(action), _p(E), _p(nu),
-                                         _p(ys), _p(xo), _p(vo), _p(Co), _p(Fo), _p(po), _p(ro), _p(go), _p(ckpt), stream), "ud_plb_step_fwd_gap")
+        args = (x, v, Cm, F, pp, pr, pg, so, action, E, nu, ys, xo, vo, Co, Fo, po, ro, go, ckpt)
+        _lib.check(L.ud_plb_step_fwd_gap(sim._h, B, *[_lib.ptr(t) for t in args], stream), "ud_plb_step_fwd_gap")
         sim._prof_end(ev)
         ctx.sim, ctx.B = sim, B
         ctx.save_for_backward(ckpt, so, action, E, nu, ys)
@@ -344,11 +338,10 @@ class _PlbStepGap(torch.autograd.Function):
         mk = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
         ox, ov, oC, oF, op, orot, ogap, oa = mk(B, N, 3), mk(B, N, 3), mk(B, N, 3, 3), mk(B, N, 3, 3), mk(B, P, 3), mk(B, P, 4), mk(B, P), mk(B, 7)
         oE, onu, oys, ofr = mk(B), mk(B), mk(B), mk(B)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _lib.stream(dev)
         ev = sim._prof_begin("bwd")
-        _lib.check(L.ud_plb_step_bwd_gap(sim._h, C.c_int(B), _p(ckpt), _p(so), _p(action), _p(E), _p(nu), _p(ys), _p(gx), _p(gv), _p(gC),
-                                         _p(gF), _p(gpp), _p(gpr), _p(gpg), _p(ox), _p(ov), _p(oC), _p(oF), _p(op), _p(orot), _p(ogap), _p(oa), _p(oE),
-                                         _p(onu), _p(oys), _p(ofr), stream), "ud_plb_step_bwd_gap")
+        args = (ckpt, so, action, E, nu, ys, gx, gv, gC, gF, gpp, gpr, gpg, ox, ov, oC, oF, op, orot, ogap, oa, oE, onu, oys, ofr)
+        _lib.check(L.ud_plb_step_bwd_gap(sim._h, B, *[_lib.ptr(t) for t in args], stream), "ud_plb_step_bwd_gap")
         sim._prof_end(ev)
         sim.ground_friction_grad = ofr if sim.ground_friction_grad is None else sim.ground_friction_grad + ofr
         return None, ox, ov, oC, oF, op, orot, ogap, None, oa, oE, onu, oys
@@ -362,9 +355,9 @@ class _PlbLossGap(torch.autograd.Function):
         x, pp, pr, pg = _c(x), _c(pp), _c(pr), _c(pg)
         loss = torch.empty((B,), dtype=torch.float64, device=x.device)
         parts = torch.empty((B, 3), dtype=torch.float64, device=x.device)
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        _lib.check(L.ud_plb_loss_fwd_gap(sim._h, C.c_int(B), _p(x), _p(pp), _p(pr), _p(pg), _p(td), _p(ts), _p(wt), C.c_int(int(soft)), _p(loss),
-                                         _p(parts), stream), "ud_plb_loss_fwd_gap")
+        stream = _lib.stream(x.device)
+        _lib.check(L.ud_plb_loss_fwd_gap(sim._h, B, *[_lib.ptr(t) for t in (x, pp, pr, pg, td, ts, wt)], int(soft), _lib.ptr(loss),
+                                         _lib.ptr(parts), stream), "ud_plb_loss_fwd_gap")
         ctx.sim, ctx.B, ctx.soft = sim, B, soft
         ctx.save_for_backward(x, pp, pr, pg, td, ts, wt)
         ctx.mark_non_differentiable(parts)
@@ -376,9 +369,9 @@ class _PlbLossGap(torch.autograd.Function):
         x, pp, pr, pg, td, ts, wt = ctx.saved_tensors
         gl = _c(gl)
         gx, gpp, gpr, gpg = torch.empty_like(x), torch.empty_like(pp), torch.empty_like(pr), torch.empty_like(pg)
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        _lib.check(L.ud_plb_loss_bwd_gap(ctx.sim._h, C.c_int(ctx.B), _p(x), _p(pp), _p(pr), _p(pg), _p(td), _p(ts), _p(wt), C.c_int(int(ctx.soft)),
-                                         _p(gl), _p(gx), _p(gpp), _p(gpr), _p(gpg), stream), "ud_plb_loss_bwd_gap")
+        stream = _lib.stream(x.device)
+        _lib.check(L.ud_plb_loss_bwd_gap(ctx.sim._h, ctx.B, *[_lib.ptr(t) for t in (x, pp, pr, pg, td, ts, wt)], int(ctx.soft),
+                                         *[_lib.ptr(t) for t in (gl, gx, gpp, gpr, gpg)], stream), "ud_plb_loss_bwd_gap")
         return None, gx, gpp, gpr, gpg, None, None, None, None
 
 
@@ -390,9 +383,9 @@ class _PlbLossRot(torch.autograd.Function):
         x, pp, pr = _c(x), _c(pp), _c(pr)
         loss = torch.empty((B,), dtype=torch.float64, device=x.device)
         parts = torch.empty((B, 3), dtype=torch.float64, device=x.device)
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        _lib.check(L.ud_plb_loss_fwd_rot(sim._h, C.c_int(B), _p(x), _p(pp), _p(pr), _p(td), _p(ts), _p(wt), C.c_int(int(soft)), _p(loss),
-                                         _p(parts), stream), "ud_plb_loss_fwd_rot")
+        stream = _lib.stream(x.device)
+        _lib.check(L.ud_plb_loss_fwd_rot(sim._h, B, *[_lib.ptr(t) for t in (x, pp, pr, td, ts, wt)], int(soft), _lib.ptr(loss),
+                                         _lib.ptr(parts), stream), "ud_plb_loss_fwd_rot")
         ctx.sim, ctx.B, ctx.soft = sim, B, soft
         ctx.save_for_backward(x, pp, pr, td, ts, wt)
         ctx.mark_non_differentiable(parts)
@@ -404,9 +397,9 @@ class _PlbLossRot(torch.autograd.Function):
         x, pp, pr, td, ts, wt = ctx.saved_tensors
         gl = _c(gl)
         gx, gpp, gpr = torch.empty_like(x), torch.empty_like(pp), torch.empty_like(pr)
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        _lib.check(L.ud_plb_loss_bwd_rot(ctx.sim._h, C.c_int(ctx.B), _p(x), _p(pp), _p(pr), _p(td), _p(ts), _p(wt), C.c_int(int(ctx.soft)),
-                                         _p(gl), _p(gx), _p(gpp), _p(gpr), stream), "ud_plb_loss_bwd_rot")
+        stream = _lib.stream(x.device)
+        _lib.check(L.ud_plb_loss_bwd_rot(ctx.sim._h, ctx.B, *[_lib.ptr(t) for t in (x, pp, pr, td, ts, wt)], int(ctx.soft),
+                                         *[_lib.ptr(t) for t in (gl, gx, gpp, gpr)], stream), "ud_plb_loss_bwd_rot")
         return None, gx, gpp, gpr, None, None, None, None
 
 
@@ -418,8 +411,8 @@ class _PlbLoss(torch.autograd.Function):
         x, pp = _c(x), _c(pp)
         loss = torch.empty((B,), dtype=torch.float64, device=x.device)
         parts = torch.empty((B, 3), dtype=torch.float64, device=x.device)
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        _lib.check(L.ud_plb_loss_fwd(sim._h, C.c_int(B), _p(x), _p(pp), _p(td), _p(ts), _p(wt), C.c_int(int(soft)), _p(loss), _p(parts),
+        stream = _lib.stream(x.device)
+        _lib.check(L.ud_plb_loss_fwd(sim._h, B, *[_lib.ptr(t) for t in (x, pp, td, ts, wt)], int(soft), _lib.ptr(loss), _lib.ptr(parts),
                                      stream), "ud_plb_loss_fwd")
         ctx.sim, ctx.B, ctx.soft = sim, B, soft
         ctx.save_for_backward(x, pp, td, ts, wt)
@@ -432,9 +425,9 @@ class _PlbLoss(torch.autograd.Function):
         x, pp, td, ts, wt = ctx.saved_tensors
         gl = _c(gl)
         gx, gpp = torch.empty_like(x), torch.empty_like(pp)
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        _lib.check(L.ud_plb_loss_bwd(ctx.sim._h, C.c_int(ctx.B), _p(x), _p(pp), _p(td), _p(ts), _p(wt), C.c_int(int(ctx.soft)), _p(gl),
-                                     _p(gx), _p(gpp), stream), "ud_plb_loss_bwd")
+        stream = _lib.stream(x.device)
+        _lib.check(L.ud_plb_loss_bwd(ctx.sim._h, ctx.B, *[_lib.ptr(t) for t in (x, pp, td, ts, wt)], int(ctx.soft), _lib.ptr(gl),
+                                     _lib.ptr(gx), _lib.ptr(gpp), stream), "ud_plb_loss_bwd")
         return None, gx, gpp, None, None, None, None
 
 
@@ -451,9 +444,9 @@ class _PlbDensitySeq(torch.autograd.Function):
             sign = torch.empty((int(L.ud_plb_density_seq_sign_bytes(sim._h, M)) // 8,), dtype=torch.int64, device=dev)
         nbytes = int(L.ud_plb_density_seq_work_bytes(sim._h, M)) if work_bytes is None else int(work_bytes)
         work = torch.empty((max(nbytes // 8, 1),), dtype=torch.float64, device=dev)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(L.ud_plb_density_seq_fwd(sim._h, M, _p(x), _p(targets), int(targets.shape[0]), _p(index), _p(loss), _p(sign), _p(work),
-                                            nbytes, stream), "ud_plb_density_seq_fwd")
+        stream = _lib.stream(dev)
+        _lib.check(L.ud_plb_density_seq_fwd(sim._h, M, _lib.ptr(x), _lib.ptr(targets), int(targets.shape[0]),
+                                            *[_lib.ptr(t) for t in (index, loss, sign, work)], nbytes, stream), "ud_plb_density_seq_fwd")
         ctx.sim, ctx.M = sim, M
         ctx.save_for_backward(x, sign)
         return loss
@@ -463,8 +456,9 @@ class _PlbDensitySeq(torch.autograd.Function):
         x, sign = ctx.saved_tensors
         gl = _c(gl)
         gx = torch.empty_like(x)
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        _lib.check(_lib.lib().ud_plb_density_seq_bwd(ctx.sim._h, ctx.M, _p(x), _p(sign), _p(gl), _p(gx), stream), "ud_plb_density_seq_bwd")
+        stream = _lib.stream(x.device)
+        _lib.check(_lib.lib().ud_plb_density_seq_bwd(ctx.sim._h, ctx.M, *[_lib.ptr(t) for t in (x, sign, gl, gx)], stream),
+                   "ud_plb_density_seq_bwd")
         return None, gx, None, None, None
 
 
@@ -544,12 +538,12 @@ class PlbSimulator:
 
     def launch_plan(self, B=None):
         """ud_plb_launch_plan: 1 = multi-kernel path, 2 = one persistent launch per step call and direction"""
-        return int(_lib.lib().ud_plb_launch_plan(self._h, C.c_int(self.batch_size if B is None else B)))
+        return int(_lib.lib().ud_plb_launch_plan(self._h, self.batch_size if B is None else B))
 
     def check_status(self):
         """Synchronises the current stream; raises if a workgroup of the persistent kernels gave up waiting (outputs NaN); the handle is usable
         again afterwards (ud_plb_poll_timeouts resets its exchange arena)."""
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        stream = _lib.stream(self.device)
         n = int(_lib.lib().ud_plb_poll_timeouts(self._h, stream))
         if n != 0:
             raise _lib.UnidomError(_lib.lib().ud_last_error().decode())
@@ -616,8 +610,8 @@ class PlbSimulator:
         x = _c(state.x)
         B, n = x.shape[0], self.n_grid
         gm = torch.empty((B, n, n, n), dtype=torch.float64, device=x.device)
-        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        _lib.check(_lib.lib().ud_plb_grid_mass(self._h, C.c_int(B), _p(x), _p(gm), stream), "ud_plb_grid_mass")
+        stream = _lib.stream(x.device)
+        _lib.check(_lib.lib().ud_plb_grid_mass(self._h, B, _lib.ptr(x), _lib.ptr(gm), stream), "ud_plb_grid_mass")
         return gm
 
     def density_seq_loss(self, x, targets, index=None, work_bytes=None):
@@ -659,8 +653,9 @@ class PlbSimulator:
         # always given: with both arrays the minima are taken by many workgroups per item (include/unidom_hip.h)
         mab = torch.empty((M, Na), dtype=torch.float64, device=self.device)
         mba = torch.empty((M, Nb), dtype=torch.float64, device=self.device)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(_lib.lib().ud_plb_chamfer(M, int(Na), _p(af), int(Tb), int(Nb), _p(b), _p(idx), _p(out), _p(mab), _p(mba), stream), "ud_plb_chamfer")
+        stream = _lib.stream(self.device)
+        _lib.check(_lib.lib().ud_plb_chamfer(M, int(Na), _lib.ptr(af), int(Tb), int(Nb), *[_lib.ptr(t) for t in (b, idx, out, mab, mba)],
+                                             stream), "ud_plb_chamfer")
         if return_mins:
             return out.reshape(lead), mab.reshape(lead + (Na,)), mba.reshape(lead + (Nb,))
         return out.reshape(lead)

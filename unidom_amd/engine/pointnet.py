@@ -7,7 +7,6 @@ restatement on the product path); the 1x1-conv stack, the activation and the max
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 
 import torch
@@ -19,14 +18,6 @@ def _f32(t):
     return t.detach().to(torch.float32).contiguous()
 
 
-def _stream(t):
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
-def _p(t):
-    return C.c_void_p(0) if t is None else C.c_void_p(t.data_ptr())
-
-
 def farthest_point_sample(xyz, npoint):
     """(idx [B,npoint] int32, new_xyz [B,npoint,3]): farthest_point_sample + gather_point (ud_pc_fps).  idx[:,0] = 0; a tie goes to the
     lowest index; npoint > n is legal (index 0 repeats once every point is taken).  No gradient: `group_points` routes new_xyz's
@@ -35,7 +26,7 @@ def farthest_point_sample(xyz, npoint):
     B, n, _ = xyz.shape
     idx = torch.empty((B, int(npoint)), dtype=torch.int32, device=xyz.device)
     new_xyz = torch.empty((B, int(npoint), 3), dtype=torch.float32, device=xyz.device)
-    _lib.check(_lib.lib().ud_pc_fps(B, n, int(npoint), _p(xyz), _p(idx), _p(new_xyz), _stream(xyz)), "ud_pc_fps")
+    _lib.check(_lib.lib().ud_pc_fps(B, n, int(npoint), _lib.ptr(xyz), _lib.ptr(idx), _lib.ptr(new_xyz), _lib.stream(xyz.device)), "ud_pc_fps")
     return idx, new_xyz
 
 
@@ -47,7 +38,7 @@ def query_ball_point(radius, nsample, xyz, new_xyz):
     m = new_xyz.shape[1]
     idx = torch.empty((B, m, int(nsample)), dtype=torch.int32, device=xyz.device)
     cnt = torch.empty((B, m), dtype=torch.int32, device=xyz.device)
-    _lib.check(_lib.lib().ud_pc_ball_query(B, n, m, float(radius), int(nsample), _p(xyz), _p(new_xyz), _p(idx), _p(cnt), _stream(xyz)),
+    _lib.check(_lib.lib().ud_pc_ball_query(B, n, m, float(radius), int(nsample), *[_lib.ptr(t) for t in (xyz, new_xyz, idx, cnt)], _lib.stream(xyz.device)),
                "ud_pc_ball_query")
     return idx, cnt
 
@@ -62,7 +53,7 @@ class _GroupPoints(torch.autograd.Function):
         f = None if feats is None else _f32(feats)
         idx = idx.contiguous()
         out = torch.empty((B, m, nsample, 3 + Cf), dtype=torch.float32, device=x.device)
-        _lib.check(_lib.lib().ud_pc_group_fwd(B, n, m, nsample, Cf, _p(x), _p(f), _p(nx), _p(idx), _p(out), _stream(x)), "ud_pc_group_fwd")
+        _lib.check(_lib.lib().ud_pc_group_fwd(B, n, m, nsample, Cf, *[_lib.ptr(t) for t in (x, f, nx, idx, out)], _lib.stream(x.device)), "ud_pc_group_fwd")
         ctx.shape = (B, n, m, nsample, Cf)
         ctx.save_for_backward(idx, None if centre_idx is None else centre_idx.contiguous())
         return out
@@ -75,7 +66,7 @@ class _GroupPoints(torch.autograd.Function):
         mk = lambda *s: torch.empty(s, dtype=torch.float32, device=g.device)
         g_xyz, g_new = mk(B, n, 3), mk(B, m, 3)
         g_feats = mk(B, n, Cf) if Cf else None
-        _lib.check(_lib.lib().ud_pc_group_bwd(B, n, m, nsample, Cf, _p(idx), _p(centre_idx), _p(g), _p(g_xyz), _p(g_feats), _p(g_new), _stream(g)),
+        _lib.check(_lib.lib().ud_pc_group_bwd(B, n, m, nsample, Cf, *[_lib.ptr(t) for t in (idx, centre_idx, g, g_xyz, g_feats, g_new)], _lib.stream(g.device)),
                    "ud_pc_group_bwd")
         # with centre_idx the centres' cotangent is already inside g_xyz: new_xyz was a function of xyz, not an input of its own
         return g_xyz, g_feats, (None if centre_idx is not None else g_new), None, None

@@ -15,10 +15,6 @@ import torch
 from ... import _lib
 
 
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 class ChamferFn(torch.autograd.Function):
     """calc_chamfer(x [B,P,3], y [Q,3]) -> [B]; gradient w.r.t. x only (y is the fixed goal cloud)."""
 
@@ -30,8 +26,8 @@ class ChamferFn(torch.autograd.Function):
         out = torch.empty((B,), dtype=torch.float32, device=x.device)
         ixy = torch.empty((B, P), dtype=torch.int32, device=x.device)
         iyx = torch.empty((B, Q), dtype=torch.int32, device=x.device)
-        _lib.check(_lib.lib().ud_chamfer_fwd(C.c_int(B), C.c_int(P), C.c_int(Q), _lib.ptr(x), _lib.ptr(y), _lib.ptr(out),
-                                             _lib.ptr(ixy), _lib.ptr(iyx), _stream(x.device)), "ud_chamfer_fwd")
+        _lib.check(_lib.lib().ud_chamfer_fwd(B, P, Q, *[_lib.ptr(t) for t in (x, y, out, ixy, iyx)], _lib.stream(x.device)),
+                   "ud_chamfer_fwd")
         ctx.save_for_backward(x, y, ixy, iyx)
         return out
 
@@ -41,8 +37,8 @@ class ChamferFn(torch.autograd.Function):
         B, P, Q = x.shape[0], x.shape[1], y.shape[0]
         g = g.to(torch.float32).contiguous()
         gx = torch.empty_like(x)
-        _lib.check(_lib.lib().ud_chamfer_bwd(C.c_int(B), C.c_int(P), C.c_int(Q), _lib.ptr(x), _lib.ptr(y), _lib.ptr(ixy),
-                                             _lib.ptr(iyx), _lib.ptr(g), _lib.ptr(gx), _stream(x.device)), "ud_chamfer_bwd")
+        _lib.check(_lib.lib().ud_chamfer_bwd(B, P, Q, *[_lib.ptr(t) for t in (x, y, ixy, iyx, g, gx)], _lib.stream(x.device)),
+                   "ud_chamfer_bwd")
         return gx, None
 
 
@@ -58,8 +54,8 @@ class PnpContactFn(torch.autograd.Function):
         macro = torch.empty((40, B, 8), dtype=torch.float32, device=xc.device)
         contact = torch.empty((B,), dtype=torch.float32, device=xc.device)
         idx = torch.empty((B,), dtype=torch.int32, device=xc.device)
-        _lib.check(_lib.lib().ud_cloth_pnp_fwd(C.c_int(B), C.c_int(P), _lib.ptr(a), _lib.ptr(p0), _lib.ptr(xc), _lib.ptr(macro),
-                                               _lib.ptr(contact), _lib.ptr(idx), _stream(xc.device)), "ud_cloth_pnp_fwd")
+        _lib.check(_lib.lib().ud_cloth_pnp_fwd(B, P, _lib.ptr(a), _lib.ptr(p0), _lib.ptr(xc), _lib.ptr(macro),
+                                               _lib.ptr(contact), _lib.ptr(idx), _lib.stream(xc.device)), "ud_cloth_pnp_fwd")
         ctx.save_for_backward(a, xc, contact, idx)
         # an unused output's cotangent arrives as None, not as zeros: the kernel then adds no contact term (aux_reward off), where
         # 0 * d contact would be NaN with the pick on a particle
@@ -76,9 +72,9 @@ class PnpContactFn(torch.autograd.Function):
         ga = torch.empty_like(a)
         gp = torch.empty((B, 4), dtype=torch.float32, device=xc.device)
         gx = torch.empty_like(xc)
-        _lib.check(_lib.lib().ud_cloth_pnp_bwd(C.c_int(B), C.c_int(P), _lib.ptr(a), _lib.ptr(xc), _lib.ptr(contact), _lib.ptr(idx),
+        _lib.check(_lib.lib().ud_cloth_pnp_bwd(B, P, _lib.ptr(a), _lib.ptr(xc), _lib.ptr(contact), _lib.ptr(idx),
                                                _lib.ptr(g_macro), _lib.ptr(g_contact), _lib.ptr(ga), _lib.ptr(gp), _lib.ptr(gx),
-                                               _stream(xc.device)), "ud_cloth_pnp_bwd")
+                                               _lib.stream(xc.device)), "ud_cloth_pnp_bwd")
         return ga, gp, gx
 
 
@@ -97,7 +93,7 @@ class DepthFn(torch.autograd.Function):
         img = torch.empty((M, H, W), dtype=torch.float32, device=x.device)
         owner = torch.empty((M, P), dtype=torch.int32, device=x.device) if ctx.needs_input_grad[0] else None
         _lib.check(_lib.lib().ud_cloth_depth_fwd(M, P, H, W, DepthFn.PIXEL_SIZE, DepthFn.Z_OFFSET, _lib.ptr(x), _lib.ptr(img),
-                                                 _lib.ptr(owner), _stream(x.device)), "ud_cloth_depth_fwd")
+                                                 _lib.ptr(owner), _lib.stream(x.device)), "ud_cloth_depth_fwd")
         ctx.save_for_backward(owner)
         return img
 
@@ -108,7 +104,7 @@ class DepthFn(torch.autograd.Function):
         g = g.to(torch.float32).contiguous()
         gx = torch.empty((M, P, 3), dtype=torch.float32, device=g.device)
         _lib.check(_lib.lib().ud_cloth_depth_bwd(M, P, DepthFn.H, DepthFn.W, _lib.ptr(owner), _lib.ptr(g), _lib.ptr(gx),
-                                                 _stream(g.device)), "ud_cloth_depth_bwd")
+                                                 _lib.stream(g.device)), "ud_cloth_depth_bwd")
         return gx
 
 
@@ -150,9 +146,8 @@ class FocusFn(torch.autograd.Function):
         B, N, S = x.shape[0], x.shape[1], pos[0].shape[1] if pos else 1
         xo, po = torch.empty_like(x), [torch.empty_like(p) for p in pos]
         shift = torch.empty((B, 3), dtype=torch.float32, device=x.device)
-        _lib.check(_lib.lib().ud_mpm_focus_fwd(C.c_int(B), C.c_int(N), C.c_int(len(pos)), C.c_int(S), C.c_float(center[0]),
-                                               C.c_float(center[2]), _lib.ptr(x), _ptr_array(pos), _lib.ptr(xo), _ptr_array(po),
-                                               _lib.ptr(shift), _stream(x.device)), "ud_mpm_focus_fwd")
+        _lib.check(_lib.lib().ud_mpm_focus_fwd(B, N, len(pos), S, center[0], center[2], _lib.ptr(x), _ptr_array(pos), _lib.ptr(xo),
+                                               _ptr_array(po), _lib.ptr(shift), _lib.stream(x.device)), "ud_mpm_focus_fwd")
         ctx.dims = (B, N, len(pos), S, x.device)
         ctx.set_materialize_grads(False)
         return (xo, shift, *po)
@@ -163,8 +158,8 @@ class FocusFn(torch.autograd.Function):
         c = lambda g: None if g is None else g.to(torch.float32).contiguous()
         g_xo, g_shift, g_po = c(g_xo), c(g_shift), [c(g) for g in g_po]
         gx = torch.empty((B, N, 3), dtype=torch.float32, device=dev)
-        _lib.check(_lib.lib().ud_mpm_focus_bwd(C.c_int(B), C.c_int(N), C.c_int(P), C.c_int(S), _lib.ptr(g_xo), _ptr_array(g_po),
-                                               _lib.ptr(g_shift), _lib.ptr(gx), _stream(dev)), "ud_mpm_focus_bwd")
+        _lib.check(_lib.lib().ud_mpm_focus_bwd(B, N, P, S, _lib.ptr(g_xo), _ptr_array(g_po), _lib.ptr(g_shift), _lib.ptr(gx),
+                                               _lib.stream(dev)), "ud_mpm_focus_bwd")
         return (None, gx, *g_po)
 
 
@@ -186,9 +181,9 @@ class FinishFn(torch.autograd.Function):
         reward = torch.empty((B,), dtype=torch.float32, device=x.device)
         obs = torch.empty((B, 6 * N + 3 * S), dtype=torch.float32, device=x.device)
         _lib.check(_lib.lib().ud_mpm_finish_fwd(
-            C.c_int(B), C.c_int(N), C.c_int(len(pos)), C.c_int(S), C.c_int(Q), *[_lib.ptr(t) for t in (x, v, Cm, F, J, shift)], _ptr_array(pos),
+            B, N, len(pos), S, Q, *[_lib.ptr(t) for t in (x, v, Cm, F, J, shift)], _ptr_array(pos),
             _lib.ptr(goal), *[_lib.ptr(t) for t in (xo, vo, Co, Fo, Jo)], _ptr_array(po), _lib.ptr(reward), _lib.ptr(obs),
-            _stream(x.device)), "ud_mpm_finish_fwd")
+            _lib.stream(x.device)), "ud_mpm_finish_fwd")
         ctx.save_for_backward(x, v, Cm, F, shift, goal, reward)
         ctx.dims = (B, N, len(pos), S)
         ctx.set_materialize_grads(False)
@@ -205,9 +200,9 @@ class FinishFn(torch.autograd.Function):
         opos = [torch.empty((B, S, 3), dtype=torch.float32, device=x.device) for _ in range(P)]
         osh = None if shift is None else torch.empty((B, 3), dtype=torch.float32, device=x.device)
         _lib.check(_lib.lib().ud_mpm_finish_bwd(
-            C.c_int(B), C.c_int(N), C.c_int(P), C.c_int(S), C.c_int(goal.shape[0]), *[_lib.ptr(t) for t in (x, v, Cm, F, shift, goal, reward)],
+            B, N, P, S, goal.shape[0], *[_lib.ptr(t) for t in (x, v, Cm, F, shift, goal, reward)],
             *[_lib.ptr(t) for t in (g_x, g_v, g_C, g_F)], _ptr_array(g_po), _lib.ptr(g_reward), _lib.ptr(g_obs),
-            *[_lib.ptr(t) for t in (ox, ov, oC, oF)], _ptr_array(opos), _lib.ptr(osh), _stream(x.device)), "ud_mpm_finish_bwd")
+            *[_lib.ptr(t) for t in (ox, ov, oC, oF)], _ptr_array(opos), _lib.ptr(osh), _lib.stream(x.device)), "ud_mpm_finish_bwd")
         return (ox, ov, oC, oF, None, osh, None, *opos)
 
 
