@@ -319,7 +319,7 @@ int ud_mpm_step_bwd(ud_mpm* h, int B, const void* ckpt, const float* prim_size, 
  * with cv the collider velocity, w = u - cv, t = w - min(w.D, 0) D and t' = t / |t| max(0, |t| + (w.D) prim_friction) where
  * w.D < 0 (|t| = sqrt(t.t + 1e-8)).  Its adjoint holds the two branch decisions constant and reaches u, P_f (through p, dist,
  * D, influence, cv) and P_{f+1}; orientation, height, radius, friction and softness are not leaves.  The contact loss takes the
- * Capsule's distance.  Without rot_state the orientation is a handle constant (only primitive 0 is actuated, three action dimensions).
+ * Capsule's distance.  Without rot_state the orientation is a handle constant (three action dimensions per actuated primitive).
  * A handle with a Capsule, or with an action_scale other than (1, 1, 1), runs the multi-kernel path only.
  * 3 Box, 4 Cylinder, 5 Torus (primitives.py:241-269, 176-202, 211-231): the same contact model, with the kind's own _sdf / _normal of the
  * local point pl in place of the Capsule's; length(x) = sqrt(x.x + 1e-14) everywhere.  Box (prim_shape = size, three half extents):
@@ -336,7 +336,7 @@ int ud_mpm_step_bwd(ud_mpm* h, int B, const void* ckpt, const float* prim_size, 
  * reference's Primitive does (primive_base.py:31-38), turned once per substep (:117-121):
  *   a = clip(action, -1, 1) (its cotangent passes at equality and is zero outside);
  *   kinds 0 and 1:  v = a[0:3] action_scale / substeps, w = a[3:6] action_scale_w / substeps (0 with three action dimensions and for
- *     primitive 1);  pos[f+1] = clamp(pos[f] + v, lower_bound, upper_bound);  rot[f+1] = qmul(w2quat(w), rot[f]);
+ *     an unactuated primitive 1; an actuated one: "Two actuated primitives" below);  pos[f+1] = clamp(pos[f] + v, lower_bound, upper_bound);  rot[f+1] = qmul(w2quat(w), rot[f]);
  *   kind 2, the RollingPin (primitives.py:83-99; the Capsule's geometry and contact):  (dw, dth, dy) = a action_scale / substeps;
  *     y_dir = qrot(rot[f], (0, -1, 0));  x_dir = cross((0, 1, 0), y_dir) dw 0.03, x_dir.y = dy;  pos[f+1] = clamp(pos[f] + x_dir);
  *     rot[f+1] = qmul(w2quat((0, -dth, 0)), qmul(rot[f], w2quat((0, dw, 0)))) -- the position step depends on the rotation.
@@ -363,8 +363,22 @@ int ud_mpm_step_bwd(ud_mpm* h, int B, const void* ckpt, const float* prim_size, 
  *   Through max(gap - gap_vel, min_gap) the cotangent passes to gap[f] and -gap_vel where gap[f] - gap_vel > min_gap and is zero where it is
  *   smaller; at exact equality it is UNSPECIFIED.  The right-multiplied step has its own adjoint; w's cotangent on the |w| <= 1e-9 arm is 0 as
  *   above.  h, r, min_gap and the scales are not leaves.  Only primitive 0 can be a Chopsticks, on rot_state with action_dim = 7; primitive 1 is
- *   the unactuated sticky Sphere of every rot_state handle (its gap entry is carried along unchanged).  Multi-kernel path only.
+ *   a sticky Sphere that never moves or, with action_dim1 != 0, an actuated kind 0, 1, 3, 4 or 5 as on every rot_state handle; its gap entry is
+ *   carried along unchanged.  Multi-kernel path only.
  *   Specification: tests/plb_chopsticks_twin.py (the reference ships no chopsticks.yml and no recording).
+ * Two actuated primitives (action_dim1 != 0; engine/primitive/primitives.py:280-319: Primitives gives every primitive its own action.dim and slices
+ * one flat action vector by the running offsets action_dims, set_action :307-311; get_grad concatenates the per-primitive gradients, :313-319).
+ *   A0 = what primitive 0 takes (3, or action_dim: 6, the Chopsticks' 7), A = A0 + action_dim1.  On all three entry-point families (plain, _rot,
+ *   _gap) action and g_action are [B, A]: primitive 0's block in columns 0 .. A0 - 1, exactly as without the field, primitive 1's in columns
+ *   A0 .. A - 1.  a = clip(action, -1, 1) per component over the whole row (its cotangent passes at equality and is zero outside).
+ *   Primitive 1 ALWAYS follows the base class, also beside a RollingPin or a Chopsticks: v = a1[0:3] action_scale1 / substeps, w = a1[3:6]
+ *   action_scale_w1 / substeps (0 with action_dim1 = 3);  pos[f+1] = clamp(pos[f] + v, lower_bound, upper_bound);  rot[f+1] = qmul(w2quat(w),
+ *   rot[f]) (left multiplication; the |w| <= 1e-9 arm sends the cotangent 0 to w, as for primitive 0).
+ *   With action_dim1 != 0 primitive 1 of a rot_state handle may be kind 0, 1, 3, 4 or 5 (its rotation is read by the contact and the loss and is
+ *   a leaf of both); without rot_state it may be what it may be with action_dim1 = 0.  RollingPin (2) and Chopsticks (6) stay primitive 0 only.
+ *   A Sphere + Sphere handle with action_dim1 = 3 and both unit scales runs the persistent path; any other such handle the multi-kernel path.
+ *   The checkpoint layout does not change: the trajectories already carry a primitive axis.  Specification: tests/plb_multi_twin.py (the
+ *   reference ships no two-handed task).
  * Parity for these entry points is UNPINNED: taichi is absent and the reference ships no recording of this path; the torch
  * restatements (oracle/twin/plb_twin_torch.py, tests/plb_prim_twin.py for the Capsule) are the specification the kernels are held to.
  * ------------------------------------------------------------------------------------------------ */
@@ -377,7 +391,8 @@ typedef struct {
   double dt;             /* 0.5e-4 / (quality * 0.5)                  :21 */
   double gravity[3];     /* SIMULATOR.gravity (the kernel applies x30, :205) */
   double ground_friction;
-  int n_primitives;      /* 1 or 2 primitives (Spheres unless prim_kind says otherwise); only primitive 0 is actuated (3 action dims, or action_dim) */
+  int n_primitives;      /* 1 or 2 primitives (Spheres unless prim_kind says otherwise); primitive 0 is actuated (3 action dims, or action_dim),
+                            primitive 1 only with action_dim1 below */
   double radius[2];
   double lower_bound[3], upper_bound[3];   /* primitive xyz_limit */
   int grid_ckpt_cells;   /* 0: ud_plb_step_bwd runs p2g again for every substep (substep_grad recomputes the whole substep,
@@ -414,8 +429,8 @@ typedef struct {
   double action_scale[3];    /* primitive 0: v = clip(action, -1, 1) * action_scale / substeps (set_velocity); all zero = (1, 1, 1).  Any
                                 other value: multi-kernel path, as with a Capsule */
   int rot_state;             /* nonzero: every primitive's orientation is per-env state, passed through the *_rot entry points (prim_rot above is
-                                then unused by the kernels).  Primitive 0 must be kind 1 to 5, primitive 1 (unactuated, never moves) a sticky
-                                Sphere: anything else, and path = 2, UD_ERR_UNSUPPORTED */
+                                then unused by the kernels).  Primitive 0 must be kind 1 to 6; primitive 1 a sticky Sphere that never moves or,
+                                with action_dim1 != 0, an actuated kind 0, 1, 3, 4 or 5: anything else, and path = 2, UD_ERR_UNSUPPORTED */
   int action_dim;            /* 0 or 3: three action dimensions.  6: (v, w) of the base class (set_velocity, primive_base.py:185-193); needs
                                 rot_state (UD_ERR_INVALID without).  7: the Chopsticks' (v, w, gap_vel); UD_ERR_INVALID with any other kind */
   double action_scale_w[3];  /* action.scale[3:6]: w = clip(action[3:6], -1, 1) * action_scale_w / substeps; all zero = (1, 1, 1) */
@@ -423,6 +438,12 @@ typedef struct {
                                 UD_ERR_INVALID.  Kinds 0 to 2 ignore it (zero = the handle of before) */
   double min_gap[2];         /* kind 6: Chopsticks.minimal_gap, >= 0 (the reference's default: 0.06); other kinds ignore it */
   double action_scale_gap;   /* kind 6: action.scale[6], gap_vel = clip(action[6], -1, 1) * action_scale_gap / substeps; 0 = 1 */
+  int action_dim1;           /* primitive 1's action block, behind primitive 0's A0 columns (see "Two actuated primitives" above).  0: primitive 1
+                                is unactuated, the handle of before in every respect.  3: it takes v.  6: (v, w) of the base class; needs
+                                rot_state.  Anything else, 6 without rot_state, or nonzero with n_primitives < 2: UD_ERR_INVALID */
+  double action_scale1[3];   /* primitive 1: v = clip(action[A0:A0+3], -1, 1) * action_scale1 / substeps; all zero = (1, 1, 1).  Any other
+                                value: multi-kernel path */
+  double action_scale_w1[3]; /* primitive 1: w = clip(action[A0+3:A0+6], -1, 1) * action_scale_w1 / substeps; all zero = (1, 1, 1) */
 } ud_plb_conf;
 
 int ud_plb_create(const ud_plb_conf* conf, ud_plb** out);
@@ -437,7 +458,7 @@ int ud_plb_launch_plan(const ud_plb* h, int B);
  * words nor exchange grids and writes NaN to all its outputs -- a time-out can never turn into finite-but-wrong results of later steps. */
 int ud_plb_poll_timeouts(ud_plb* h, void* stream);
 /* One env.step for B independent envs (float64 device arrays): x, v [B,N,3]; C, F [B,N,3,3]; prim_pos
- * [B,n_primitives,3]; softness [B,n_primitives]; action [B,3]; E, nu, yield_stress [B]. */
+ * [B,n_primitives,3]; softness [B,n_primitives]; action [B,A] (A = 3 + action_dim1: "Two actuated primitives" above); E, nu, yield_stress [B]. */
 int ud_plb_step_fwd(ud_plb* h, int B, const double* x, const double* v, const double* C, const double* F,
                     const double* prim_pos, const double* softness, const double* action, const double* E,
                     const double* nu, const double* yield_stress, double* x_out, double* v_out, double* C_out,
@@ -446,7 +467,7 @@ int ud_plb_step_fwd(ud_plb* h, int B, const double* x, const double* v, const do
  * the primitive trajectory and the internal spatial order of this call, consumed by ud_plb_step_bwd. */
 size_t ud_plb_ckpt_bytes(const ud_plb* h, int B);
 /* The same on a rot_state handle (UD_ERR_INVALID on any other; ud_plb_step_fwd / _bwd / ud_plb_loss_* return UD_ERR_INVALID on a
- * rot_state handle): prim_rot [B,n_primitives,4] (w, x, y, z; |q| > 0.9 is the caller's duty), action [B,action_dim], prim_rot_out
+ * rot_state handle): prim_rot [B,n_primitives,4] (w, x, y, z; |q| > 0.9 is the caller's duty), action [B,A] (A = action_dim + action_dim1), prim_rot_out
  * [B,n_primitives,4].  The checkpoint (ud_plb_ckpt_bytes) also keeps the rotation trajectory.  Launches only: no allocation, no
  * synchronisation. */
 int ud_plb_step_fwd_rot(ud_plb* h, int B, const double* x, const double* v, const double* C, const double* F,
@@ -456,7 +477,7 @@ int ud_plb_step_fwd_rot(ud_plb* h, int B, const double* x, const double* v, cons
 
 /* The same on a Chopsticks handle (prim_kind[0] = 6; UD_ERR_INVALID on any other, and ud_plb_step_fwd / _fwd_rot and their siblings return
  * UD_ERR_INVALID on a Chopsticks handle, touch no output and name the reason): prim_gap [B,n_primitives] (primitive 1's entry is carried
- * through), action [B,7], prim_gap_out [B,n_primitives].  The checkpoint also keeps the gap trajectory (ud_plb_ckpt_bytes grows for such
+ * through), action [B,A] (A = 7 + action_dim1), prim_gap_out [B,n_primitives].  The checkpoint also keeps the gap trajectory (ud_plb_ckpt_bytes grows for such
  * handles only).  Launches only: no allocation, no synchronisation; graph-capturable like its siblings. */
 int ud_plb_step_fwd_gap(ud_plb* h, int B, const double* x, const double* v, const double* C, const double* F,
                         const double* prim_pos, const double* prim_rot, const double* prim_gap, const double* softness,
@@ -466,7 +487,7 @@ int ud_plb_step_fwd_gap(ud_plb* h, int B, const double* x, const double* v, cons
 
 /* Adjoint of one env.step.  g_x, g_v [B,N,3], g_C, g_F [B,N,3,3], g_prim_pos [B,n_primitives,3]: cotangents of the
  * step's outputs (any may be NULL = zero).  Outputs: cotangents of the inputs x, v, C, F (required), of prim_pos
- * [B,n_primitives,3], of action [B,3], and per env of E, nu, yield_stress and the ground friction [B] (each may be NULL).
+ * [B,n_primitives,3], of action [B,A] (both blocks), and per env of E, nu, yield_stress and the ground friction [B] (each may be NULL).
  * softness, action, E, nu, yield_stress: the forward call's inputs again. */
 int ud_plb_step_bwd(ud_plb* h, int B, const void* ckpt, const double* softness, const double* action, const double* E,
                     const double* nu, const double* yield_stress, const double* g_x, const double* g_v, const double* g_C,
@@ -474,14 +495,14 @@ int ud_plb_step_bwd(ud_plb* h, int B, const void* ckpt, const double* softness, 
                     double* g_prim_pos0, double* g_action, double* g_E, double* g_nu, double* g_yield_stress,
                     double* g_ground_friction, void* stream);
 /* ... of ud_plb_step_fwd_rot: g_prim_rot [B,n_primitives,4] (in, may be NULL = zero), g_prim_rot0 [B,n_primitives,4] (out, may be
- * NULL), g_action [B,action_dim]. */
+ * NULL), g_action [B,A]. */
 int ud_plb_step_bwd_rot(ud_plb* h, int B, const void* ckpt, const double* softness, const double* action, const double* E,
                         const double* nu, const double* yield_stress, const double* g_x, const double* g_v, const double* g_C,
                         const double* g_F, const double* g_prim_pos, const double* g_prim_rot, double* g_x0, double* g_v0,
                         double* g_C0, double* g_F0, double* g_prim_pos0, double* g_prim_rot0, double* g_action, double* g_E,
                         double* g_nu, double* g_yield_stress, double* g_ground_friction, void* stream);
 /* ... of ud_plb_step_fwd_gap: also g_prim_gap [B,n_primitives] (in, may be NULL = zero), g_prim_gap0 [B,n_primitives] (out, may be NULL),
- * g_action [B,7]. */
+ * g_action [B,A]. */
 int ud_plb_step_bwd_gap(ud_plb* h, int B, const void* ckpt, const double* softness, const double* action, const double* E,
                         const double* nu, const double* yield_stress, const double* g_x, const double* g_v, const double* g_C,
                         const double* g_F, const double* g_prim_pos, const double* g_prim_rot, const double* g_prim_gap, double* g_x0,

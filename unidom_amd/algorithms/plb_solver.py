@@ -6,6 +6,7 @@ The reference optimises one env's action sequence [horizon, action_dim] with ti.
 `loss.backward()` through PlbSimulator.step / PlbLoss.compute_loss plays the tape.  The optimisers work on float64 device tensors.
 
     python -m unidom_amd.algorithms.plb_solver --env torus --iters 10
+    python -m unidom_amd.algorithms.plb_solver --env bimanual --iters 10     (two actuated Spheres: actions [horizon, B, 6])
 """
 from __future__ import annotations
 
@@ -134,9 +135,9 @@ def make_goal(sim, actions, softness=666.0):
 
 def main(argv=None):
     from ..engine.plb_losses import PlbLoss
-    from ..engine.plb_simulator import PlbConf, PlbSimulator, WriterConf
+    from ..engine.plb_simulator import BimanualConf, PlbConf, PlbSimulator, WriterConf
     ap = argparse.ArgumentParser(description="PLB trajectory optimisation towards a goal density (the reference's solve.py)")
-    ap.add_argument("--env", choices=["torus", "writer"], default="torus")
+    ap.add_argument("--env", choices=["torus", "writer", "bimanual"], default="torus")
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--horizon", type=int, default=5)
     ap.add_argument("--num_envs", type=int, default=1)
@@ -145,9 +146,10 @@ def main(argv=None):
     ap.add_argument("--softness", type=float, default=666.0)
     ap.add_argument("--goal_steps", type=int, default=5, help="the goal is the grid mass after this many steps of a fixed action")
     args = ap.parse_args(argv)
-    cfg = WriterConf() if args.env == "writer" else PlbConf()
+    cfg = {"writer": WriterConf, "bimanual": BimanualConf}.get(args.env, PlbConf)()
     sim = PlbSimulator(cfg, batch_size=args.num_envs)
-    push = [0.0, -0.6, 0.0] if args.env == "writer" else [0.6, 0.0, 0.0]      # the Capsule presses down / the sphere drags the torus sideways
+    # the Capsule presses down / the sphere drags the torus sideways / the two spheres push the rod's ends towards each other
+    push = {"writer": [0.0, -0.6, 0.0], "bimanual": [-0.6, 0.0, 0.0, 0.6, 0.0, 0.0]}.get(args.env, [0.6, 0.0, 0.0])
     goal_actions = torch.tensor([push] * args.goal_steps, dtype=torch.float64, device=sim.device)
     loss = PlbLoss(sim, weights=(1.0, 1.0, 1.0), soft_contact=True).load_target_density(make_goal(sim, goal_actions, args.softness))
     solver = Solver(sim, loss, horizon=args.horizon, n_iters=args.iters, softness=args.softness, optim=args.optim, init_range=0.0001, lr=args.lr)

@@ -78,9 +78,9 @@ class SolverNN:
 def main(argv=None):
     from ..engine.plb_losses import PlbLoss
     from ..engine.plb_policy import PlbPolicy
-    from ..engine.plb_simulator import MoveConf, PlbConf, PlbSimulator
+    from ..engine.plb_simulator import BimanualConf, MoveConf, PlbConf, PlbSimulator
     ap = argparse.ArgumentParser(description="PLB closed-loop policy optimisation towards a goal density (the reference's solve.py --algo nn)")
-    ap.add_argument("--env", choices=["torus", "move"], default="torus")
+    ap.add_argument("--env", choices=["torus", "move", "bimanual"], default="torus")
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--horizon", type=int, default=5)
     ap.add_argument("--num_envs", type=int, default=1)
@@ -95,9 +95,10 @@ def main(argv=None):
                     help="the last layer's initial W and b are multiplied by this (1 = the reference's initialisation as it is: on torus, whose "
                          "action scale is 1, that policy drives the sphere so hard that the state is no longer finite after three steps)")
     args = ap.parse_args(argv)
-    cfg = MoveConf() if args.env == "move" else PlbConf()
+    cfg = {"move": MoveConf, "bimanual": BimanualConf}.get(args.env, PlbConf)()
     sim = PlbSimulator(cfg, batch_size=args.num_envs)
-    push = [-0.6, 0.0, 0.0] if args.env == "move" else [0.6, 0.0, 0.0]      # the sphere pushes the rod's end in / drags the torus sideways
+    # the sphere pushes the rod's end in / drags the torus sideways / the two spheres push the rod's ends towards each other
+    push = {"move": [-0.6, 0.0, 0.0], "bimanual": [-0.6, 0.0, 0.0, 0.6, 0.0, 0.0]}.get(args.env, [0.6, 0.0, 0.0])
     goal_actions = torch.tensor([push] * args.goal_steps, dtype=torch.float64, device=sim.device)
     loss = PlbLoss(sim, weights=(1.0, 1.0, 1.0), soft_contact=True).load_target_density(make_goal(sim, goal_actions, args.softness))
     policy = PlbPolicy(sim, hidden_dims=tuple(args.hidden), activation=args.activation).init_params(args.seed)

@@ -383,17 +383,21 @@ __global__ void __launch_bounds__(1024) plb_sort(PlbArgs a, const double* x, int
 // state into the history's slot 0 in the call's spatial order; block 0 of each env also runs the prologue (primitive positions of the whole
 // step, both list counts).  order: the handle's current spatial order (arena), copied to this call's perm (the checkpoint's, for the adjoint).
 // The kinematics of a rot_state handle for one env and primitive, the whole step, serially: Primitive.forward_kinematics (primive_base.py:117-121:
-// pos[f+1] = clamp(pos[f] + v), rot[f+1] = qmul(w2quat(w), rot[f]); v, w = clip(action) * scale / substeps for primitive 0, else 0) or, r.kin == 2 and
+// pos[f+1] = clamp(pos[f] + v), rot[f+1] = qmul(w2quat(w), rot[f]); v, w = clip(action) * scale / substeps for primitive 0; primitive 1 the same from
+// its own block of the action row and its own scales (a1; a1.dim == 0: v = w = 0)) or, r.kin == 2 and
 // primitive 0, RollingPin.forward_kinematics (primitives.py:86-99), whose position step depends on the rotation.  rot[0] is used as given.
-__device__ __forceinline__ void plb_kinematics_rot(const PlbConst& c, const PlbRot& r, const PlbScale& sc, int b, int pi, const double* prim_pos,
+__device__ __forceinline__ void plb_kinematics_rot(const PlbConst& c, const PlbRot& r, const PlbScale& sc, const PlbAct1& a1, int b, int pi, const double* prim_pos,
                                                    const double* prim_rot, const double* action, double* P, double* R) {
   double pos[3], q[4], av[6] = {0, 0, 0, 0, 0, 0};
 #pragma unroll
   for (int d = 0; d < 3; ++d) { pos[d] = prim_pos[((long)b * c.np + pi) * 3 + d]; P[pi * 3 + d] = pos[d]; }
 #pragma unroll
   for (int k = 0; k < 4; ++k) { q[k] = prim_rot[((long)b * c.np + pi) * 4 + k]; R[pi * 4 + k] = q[k]; }
+  const int A = r.adim + a1.dim;
   if (pi == 0) {
-    for (int d = 0; d < r.adim; ++d) av[d] = fmin(fmax(action[(long)b * r.adim + d], -1.0), 1.0) * (d < 3 ? sc.s[d] : r.sw[d - 3]) / (double)c.S;
+    for (int d = 0; d < r.adim; ++d) av[d] = fmin(fmax(action[(long)b * A + d], -1.0), 1.0) * (d < 3 ? sc.s[d] : r.sw[d - 3]) / (double)c.S;
+  } else if (pi == 1) {
+    for (int d = 0; d < a1.dim; ++d) av[d] = fmin(fmax(action[(long)b * A + r.adim + d], -1.0), 1.0) * (d < 3 ? a1.s[d] : a1.sw[d - 3]) / (double)c.S;
   }
   if (pi == 0 && r.kin == 2) {
     const double dw = av[0], dth = av[1], dy = av[2];
@@ -427,9 +431,10 @@ __device__ __forceinline__ void plb_kinematics_rot(const PlbConst& c, const PlbR
 
 // The kinematics of a Chopsticks handle likewise (r.kin == 3): primitive 0 runs Chopsticks.forward_kinematics (primitives.py:113-128) -- seven action
 // dimensions, v, w, gap_vel = clip(action) * (scale, scale_w, scale_gap) / substeps; gap[f+1] = max(gap[f] - gap_vel, minimal_gap), pos[f+1] =
-// clamp(pos[f] + v), rot[f+1] = qmul(rot[f], w2quat(w)): the RIGHT multiplication -- primitive 1, the unactuated Sphere, the base class's with
-// v = w = 0 and a gap that stays what it was given.  Gp: the env's gap trajectory [S+1][np]; gap_out: the caller's prim_gap_out of the env.
-__device__ __forceinline__ void plb_kinematics_gap(const PlbConst& c, const PlbRot& r, const PlbGap& g, const PlbScale& sc, int b, int pi, const double* prim_pos,
+// clamp(pos[f] + v), rot[f+1] = qmul(rot[f], w2quat(w)): the RIGHT multiplication -- primitive 1 the base class's (left multiplication) with v, w from
+// its own block behind the seven (a1; a1.dim == 0: v = w = 0) and a gap that stays what it was given.  Gp: the env's gap trajectory [S+1][np];
+// gap_out: the caller's prim_gap_out of the env.
+__device__ __forceinline__ void plb_kinematics_gap(const PlbConst& c, const PlbRot& r, const PlbGap& g, const PlbScale& sc, const PlbAct1& a1, int b, int pi, const double* prim_pos,
                                                    const double* prim_rot, const double* action, double* P, double* R, double* Gp, double* gap_out) {
   double pos[3], q[4], av[7] = {0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
@@ -438,9 +443,12 @@ __device__ __forceinline__ void plb_kinematics_gap(const PlbConst& c, const PlbR
   for (int k = 0; k < 4; ++k) { q[k] = prim_rot[((long)b * c.np + pi) * 4 + k]; R[pi * 4 + k] = q[k]; }
   double gap = g.ext[(long)b * c.np + pi];
   Gp[pi] = gap;
+  const int A = 7 + a1.dim;
   if (pi == 0) {
 #pragma unroll
-    for (int d = 0; d < 7; ++d) av[d] = fmin(fmax(action[(long)b * 7 + d], -1.0), 1.0) * (d < 3 ? sc.s[d] : (d < 6 ? r.sw[d - 3] : g.sg)) / (double)c.S;
+    for (int d = 0; d < 7; ++d) av[d] = fmin(fmax(action[(long)b * A + d], -1.0), 1.0) * (d < 3 ? sc.s[d] : (d < 6 ? r.sw[d - 3] : g.sg)) / (double)c.S;
+  } else if (pi == 1) {
+    for (int d = 0; d < a1.dim; ++d) av[d] = fmin(fmax(action[(long)b * A + 7 + d], -1.0), 1.0) * (d < 3 ? a1.s[d] : a1.sw[d - 3]) / (double)c.S;
   }
   double dq[4];
   plb_w2quat(av + 3, dq);
@@ -473,12 +481,12 @@ __device__ __forceinline__ void plb_pack_particle(const PlbArgs& a, int b, int p
 // plb_pack of a Chopsticks handle: the prologue runs plb_kinematics_gap (prim_rot = r.ext, prim_gap = g.ext) and, the whole trajectory being known
 // here, writes prim_gap_out (g.ext_out) at once; the end of the call is plb_unpack_clear<true>, as on every rot_state handle
 __global__ void __launch_bounds__(256) plb_pack_gap(PlbArgs a, const double* x, const double* v, const double* Cm, const double* F, const int* order,
-                                                    const double* prim_pos, const double* action, PlbScale sc, PlbRot r, PlbGap g) {
+                                                    const double* prim_pos, const double* action, PlbScale sc, PlbAct1 a1, PlbRot r, PlbGap g) {
   const int b = blockIdx.y, p = blockIdx.x * blockDim.x + threadIdx.x;
   const PlbConst& c = a.c;
   if (blockIdx.x == 0) {
     if (threadIdx.x < c.np)
-      plb_kinematics_gap(c, r, g, sc, b, threadIdx.x, prim_pos, r.ext, action, a.w.pos + (long)b * (c.S + 1) * c.np * 3, r.rot + (long)b * (c.S + 1) * c.np * 4,
+      plb_kinematics_gap(c, r, g, sc, a1, b, threadIdx.x, prim_pos, r.ext, action, a.w.pos + (long)b * (c.S + 1) * c.np * 3, r.rot + (long)b * (c.S + 1) * c.np * 4,
                          g.gap + (long)b * (c.S + 1) * c.np, g.ext_out + (long)b * c.np);
     if (threadIdx.x >= 64 && threadIdx.x < 67) a.w.count[(threadIdx.x - 64) * a.B + b] = 0;
   }
@@ -488,18 +496,20 @@ __global__ void __launch_bounds__(256) plb_pack_gap(PlbArgs a, const double* x, 
 
 template <bool ROT>   // a rot_state handle: one thread per primitive runs the serial kinematics above (prim_rot = rr.r.ext)
 __global__ void __launch_bounds__(256) plb_pack(PlbArgs a, const double* x, const double* v, const double* Cm, const double* F, const int* order,
-                                                const double* prim_pos, const double* action, PlbScale sc, PlbRotArg<ROT> rr) {
+                                                const double* prim_pos, const double* action, PlbScale sc, PlbAct1 a1, PlbRotArg<ROT> rr) {
   const int b = blockIdx.y, p = blockIdx.x * blockDim.x + threadIdx.x;
   const PlbConst& c = a.c;
   if (blockIdx.x == 0) {
     if constexpr (ROT) {      // one thread per primitive
       if (threadIdx.x < c.np)
-        plb_kinematics_rot(c, rr.r, sc, b, threadIdx.x, prim_pos, rr.r.ext, action, a.w.pos + (long)b * (c.S + 1) * c.np * 3, rr.r.rot + (long)b * (c.S + 1) * c.np * 4);
+        plb_kinematics_rot(c, rr.r, sc, a1, b, threadIdx.x, prim_pos, rr.r.ext, action, a.w.pos + (long)b * (c.S + 1) * c.np * 3, rr.r.rot + (long)b * (c.S + 1) * c.np * 4);
     } else
-    if (threadIdx.x < c.np * 3) {   // pos[s+1] = clamp(pos[s] + v), v = clip(action) * scale / substeps for primitive 0 (set_velocity, primive_base.py:185-192); one thread per coordinate
-      const int pi = threadIdx.x / 3, d = threadIdx.x % 3;
+    if (threadIdx.x < c.np * 3) {   // pos[s+1] = clamp(pos[s] + v), v = clip(action) * scale / substeps (set_velocity, primive_base.py:185-192), primitive 1 from its own block
+      const int pi = threadIdx.x / 3, d = threadIdx.x % 3;     // (a1.dim == 0: v = 0); one thread per coordinate
       double* P = a.w.pos + (long)b * (c.S + 1) * c.np * 3;
-      const double pv = (pi == 0) ? fmin(fmax(action[b * 3 + d], -1.0), 1.0) * sc.s[d] / (double)c.S : 0.0;
+      const int A = 3 + a1.dim;
+      const double pv = (pi == 0) ? fmin(fmax(action[(long)b * A + d], -1.0), 1.0) * sc.s[d] / (double)c.S
+                      : (a1.dim != 0 ? fmin(fmax(action[(long)b * A + 3 + d], -1.0), 1.0) * a1.s[d] / (double)c.S : 0.0);
       double cur = prim_pos[(long)b * c.np * 3 + pi * 3 + d];
       P[pi * 3 + d] = cur;
       for (int s = 0; s < c.S; ++s) {
@@ -656,6 +666,21 @@ int ud_plb_create(const ud_plb_conf* conf, ud_plb** out) {
     const bool zero_w = sw[0] == 0 && sw[1] == 0 && sw[2] == 0;
     for (int d = 0; d < 3; ++d) h->rot.sw[d] = zero_w ? 1.0 : sw[d];
   }
+  // primitive 1's action block behind primitive 0's (action_dim1 = 0: unactuated, the handle of before)
+  if (!(conf->action_dim1 == 0 || conf->action_dim1 == 3 || conf->action_dim1 == 6)) {
+    ud::set_error("ud_plb_create: action_dim1 = %d (0: primitive 1 is unactuated, 3: it takes v, 6: (v, w))", conf->action_dim1); delete h; return UD_ERR_INVALID;
+  }
+  if (conf->action_dim1 != 0 && c.np < 2) {
+    ud::set_error("ud_plb_create: action_dim1 = %d needs a primitive 1 (n_primitives = %d)", conf->action_dim1, c.np); delete h; return UD_ERR_INVALID;
+  }
+  if (conf->action_dim1 == 6 && !h->rot_state) { ud::set_error("ud_plb_create: action_dim1 = 6 requires rot_state"); delete h; return UD_ERR_INVALID; }
+  h->act1.dim = conf->action_dim1;
+  {
+    const double *s1 = conf->action_scale1, *w1 = conf->action_scale_w1;
+    const bool zero_s = s1[0] == 0 && s1[1] == 0 && s1[2] == 0, zero_w = w1[0] == 0 && w1[1] == 0 && w1[2] == 0;
+    for (int d = 0; d < 3; ++d) { h->act1.s[d] = zero_s ? 1.0 : s1[d]; h->act1.sw[d] = zero_w ? 1.0 : w1[d]; }
+  }
+  const bool unit_scale1 = h->act1.dim == 0 || (h->act1.s[0] == 1.0 && h->act1.s[1] == 1.0 && h->act1.s[2] == 1.0);
   for (int pi = 0; pi < c.np; ++pi) {
     const int kind = conf->prim_kind[pi];
     if (kind < 0 || kind > 6) { ud::set_error("ud_plb_create: prim_kind[%d] = %d (0 Sphere, 1 Capsule, 2 RollingPin, 3 Box, 4 Cylinder, 5 Torus, 6 Chopsticks)", pi, kind); delete h; return UD_ERR_INVALID; }
@@ -674,7 +699,8 @@ int ud_plb_create(const ud_plb_conf* conf, ud_plb** out) {
     }
     if (h->rot_state) {
       if (pi == 0 && kind == 0) { ud::set_error("ud_plb_create: rot_state: primitive 0 must be a Capsule (1), a RollingPin (2), a Box (3), a Cylinder (4), a Torus (5) or a Chopsticks (6), not a sticky Sphere"); delete h; return UD_ERR_UNSUPPORTED; }
-      if (pi == 1 && kind != 0) { ud::set_error("ud_plb_create: rot_state: primitive 1 is unactuated and must be a sticky Sphere (prim_kind[1] = %d)", kind); delete h; return UD_ERR_UNSUPPORTED; }
+      if (pi == 1 && kind == 2 && h->act1.dim != 0) { ud::set_error("ud_plb_create: prim_kind[%d] = 2: a RollingPin can only be primitive 0", pi); delete h; return UD_ERR_UNSUPPORTED; }
+      if (pi == 1 && kind != 0 && h->act1.dim == 0) { ud::set_error("ud_plb_create: rot_state: primitive 1 is unactuated and must be a sticky Sphere (prim_kind[1] = %d)", kind); delete h; return UD_ERR_UNSUPPORTED; }
       if (kind == 2 && h->rot.adim != 3) { ud::set_error("ud_plb_create: the RollingPin takes three action dimensions (dw, dth, dy), action_dim = %d", conf->action_dim); delete h; return UD_ERR_UNSUPPORTED; }
       if (kind == 2) h->rot.kin = 2;
     }
@@ -711,7 +737,7 @@ int ud_plb_create(const ud_plb_conf* conf, ud_plb** out) {
     }
   }
   // The persistent kernels (plb_cluster.hip) hold the sticky Sphere and the unit action scale only: any other handle runs the multi-kernel path
-  const bool mk_only = h->gen || !unit_scale;
+  const bool mk_only = h->gen || !unit_scale || !unit_scale1;
   if (conf->path == 2 && mk_only) {
     ud::set_error("ud_plb_create: path = 2 (persistent) has no %s: such a handle runs the multi-kernel path (path = 0 or 1)",
                   h->chop ? "Chopsticks primitive (prim_kind = 6)" : h->rot_state ? "rotating primitives (rot_state)" : h->shape ? "Box, Cylinder or Torus primitive (prim_kind = 3, 4, 5)" : h->gen ? "Capsule primitive (prim_kind = 1)" : "action_scale other than (1, 1, 1)");
@@ -823,9 +849,9 @@ static int plb_step_fwd_impl(const char* who, ud_plb* h, int B, const double* x,
   const dim3 gq((lanes * h->c.N + 255) / 256, B);
   rr.ext = const_cast<double*>(prim_rot);
   gg.ext = const_cast<double*>(prim_gap); gg.ext_out = prim_gap_out;
-  if (chop) hipLaunchKernelGGL(ud::plb_pack_gap, gp, blk, 0, st, a, x, v, C, F, sorted ? (const int*)h->order : (const int*)nullptr, prim_pos, action, h->ascale, rr, gg);
-  else if (rot) hipLaunchKernelGGL(ud::plb_pack<true>, gp, blk, 0, st, a, x, v, C, F, sorted ? (const int*)h->order : (const int*)nullptr, prim_pos, action, h->ascale, ud::PlbRotArg<true>{rr});
-  else hipLaunchKernelGGL(ud::plb_pack<false>, gp, blk, 0, st, a, x, v, C, F, sorted ? (const int*)h->order : (const int*)nullptr, prim_pos, action, h->ascale, ud::PlbRotArg<false>{});
+  if (chop) hipLaunchKernelGGL(ud::plb_pack_gap, gp, blk, 0, st, a, x, v, C, F, sorted ? (const int*)h->order : (const int*)nullptr, prim_pos, action, h->ascale, h->act1, rr, gg);
+  else if (rot) hipLaunchKernelGGL(ud::plb_pack<true>, gp, blk, 0, st, a, x, v, C, F, sorted ? (const int*)h->order : (const int*)nullptr, prim_pos, action, h->ascale, h->act1, ud::PlbRotArg<true>{rr});
+  else hipLaunchKernelGGL(ud::plb_pack<false>, gp, blk, 0, st, a, x, v, C, F, sorted ? (const int*)h->order : (const int*)nullptr, prim_pos, action, h->ascale, h->act1, ud::PlbRotArg<false>{});
   // Per substep: plb_grid(f), then ONE particle launch: g2p(f) -> p2g(f + 1) (plb_g2p_p2g); p2g(0) opens the step, g2p(S - 1) closes it.
   const bool fused = true;
   const int S = h->c.S;

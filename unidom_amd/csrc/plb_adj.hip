@@ -411,8 +411,9 @@ __global__ void __launch_bounds__(256) plb_adj_unpack(PlbArgs a, int slot, doubl
   for (int d = 0; d < 9; ++d) { gC[o9 + d] = g[(6 + d) * c.Np + p]; gF[o9 + d] = g[(15 + d) * c.Np + p]; }
 }
 
-// forward_kinematics.grad + set_action in reverse: pos[s+1] = clamp(pos[s] + pv), pv = clip(action, -1, 1) * scale / S for primitive 0
-__global__ void plb_adj_epilogue(PlbArgs a, PlbScale sc, const double* action, double* g_prim_pos0, double* g_action, double* g_E, double* g_nu, double* g_ys, double* g_fric) {
+// forward_kinematics.grad + set_action in reverse: pos[s+1] = clamp(pos[s] + pv), pv = clip(action, -1, 1) * scale / S for primitive 0 and, from its
+// own block of the action row [A = 3 + a1.dim] and its own scale, for an actuated primitive 1 (a1.dim != 0)
+__global__ void plb_adj_epilogue(PlbArgs a, PlbScale sc, PlbAct1 a1, const double* action, double* g_prim_pos0, double* g_action, double* g_E, double* g_nu, double* g_ys, double* g_fric) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= a.Bcall) return;   // g_action, g_E, ... are the caller's [Bcall] arrays
   const PlbConst& c = a.c;
@@ -420,8 +421,11 @@ __global__ void plb_adj_epilogue(PlbArgs a, PlbScale sc, const double* action, d
   double* G = a.w.gpos + (long)b * (c.S + 1) * c.np * 3;
   for (int pi = 0; pi < c.np; ++pi)
     for (int d = 0; d < 3; ++d) {
-      const double raw = (pi == 0) ? action[b * 3 + d] : 0.0;
-      const double pv = (pi == 0) ? fmin(fmax(raw, -1.0), 1.0) * sc.s[d] / (double)c.S : 0.0;
+      const bool act = pi == 0 || (pi == 1 && a1.dim != 0);
+      const long col = (long)b * (3 + a1.dim) + pi * 3 + d;
+      const double scale = (pi == 0) ? sc.s[d] : a1.s[d];
+      const double raw = act ? action[col] : 0.0;
+      const double pv = act ? fmin(fmax(raw, -1.0), 1.0) * scale / (double)c.S : 0.0;
       double gpv = 0.0;
       for (int s = c.S - 1; s >= 0; --s) {
         const double un = P[(s * c.np + pi) * 3 + d] + pv;
@@ -431,7 +435,7 @@ __global__ void plb_adj_epilogue(PlbArgs a, PlbScale sc, const double* action, d
         gpv += g;
       }
       if (g_prim_pos0) g_prim_pos0[((long)b * c.np + pi) * 3 + d] = G[pi * 3 + d];
-      if (pi == 0 && g_action) g_action[b * 3 + d] = (raw >= -1.0 && raw <= 1.0) ? gpv * sc.s[d] / (double)c.S : 0.0;
+      if (act && g_action) g_action[col] = (raw >= -1.0 && raw <= 1.0) ? gpv * scale / (double)c.S : 0.0;
     }
   if (g_E) g_E[b] = a.w.gpar[b * 4];
   if (g_nu) g_nu[b] = a.w.gpar[b * 4 + 1];
@@ -441,8 +445,9 @@ __global__ void plb_adj_epilogue(PlbArgs a, PlbScale sc, const double* action, d
 
 // The same for a rot_state handle, one thread per env: f = S - 1 ... 0 through the adjoint of plb_kinematics_rot (plb.hip) -- the clamp passes where it
 // is inactive, qmul with its normalisation, w2quat (its identity arm sends 0 to w), and for the RollingPin the position step's dependence on
-// rotation[f] -- from gpos / grot (the step's output cotangents plus what the grid-op adjoints added) to g_prim_pos0, g_prim_rot0, g_action [B,adim].
-__global__ void __launch_bounds__(64) plb_adj_epilogue_rot(PlbArgs a, PlbRot r, PlbScale sc, const double* action, double* g_prim_pos0, double* g_prim_rot0, double* g_action,
+// rotation[f] -- from gpos / grot (the step's output cotangents plus what the grid-op adjoints added) to g_prim_pos0, g_prim_rot0, g_action [B,A], A =
+// adim + a1.dim: an actuated primitive 1 runs the base class's sweep with its own block (columns adim ..) and scales.
+__global__ void __launch_bounds__(64) plb_adj_epilogue_rot(PlbArgs a, PlbRot r, PlbScale sc, PlbAct1 a1, const double* action, double* g_prim_pos0, double* g_prim_rot0, double* g_action,
                                      double* g_E, double* g_nu, double* g_ys, double* g_fric) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= a.Bcall) return;   // g_action, g_prim_rot0, ... are the caller's [Bcall] arrays
@@ -453,10 +458,16 @@ __global__ void __launch_bounds__(64) plb_adj_epilogue_rot(PlbArgs a, PlbRot r, 
   double* GR = r.grot + (long)b * (c.S + 1) * c.np * 4;
   for (int pi = 0; pi < c.np; ++pi) {
     double raw[6] = {0, 0, 0, 0, 0, 0}, av[6] = {0, 0, 0, 0, 0, 0}, gav[6] = {0, 0, 0, 0, 0, 0};
+    const int A = r.adim + a1.dim;
     if (pi == 0) {
       for (int d = 0; d < r.adim; ++d) {
-        raw[d] = action[(long)b * r.adim + d];
+        raw[d] = action[(long)b * A + d];
         av[d] = fmin(fmax(raw[d], -1.0), 1.0) * (d < 3 ? sc.s[d] : r.sw[d - 3]) / (double)c.S;
+      }
+    } else if (pi == 1) {
+      for (int d = 0; d < a1.dim; ++d) {
+        raw[d] = action[(long)b * A + r.adim + d];
+        av[d] = fmin(fmax(raw[d], -1.0), 1.0) * (d < 3 ? a1.s[d] : a1.sw[d - 3]) / (double)c.S;
       }
     }
     if (pi == 0 && r.kin == 2) {
@@ -515,7 +526,10 @@ __global__ void __launch_bounds__(64) plb_adj_epilogue_rot(PlbArgs a, PlbRot r, 
       if (g_prim_rot0) g_prim_rot0[((long)b * c.np + pi) * 4 + k] = GR[pi * 4 + k];
     if (pi == 0 && g_action)
       for (int d = 0; d < r.adim; ++d)
-        g_action[(long)b * r.adim + d] = (raw[d] >= -1.0 && raw[d] <= 1.0) ? gav[d] * (d < 3 ? sc.s[d] : r.sw[d - 3]) / (double)c.S : 0.0;
+        g_action[(long)b * A + d] = (raw[d] >= -1.0 && raw[d] <= 1.0) ? gav[d] * (d < 3 ? sc.s[d] : r.sw[d - 3]) / (double)c.S : 0.0;
+    if (pi == 1 && g_action)
+      for (int d = 0; d < a1.dim; ++d)
+        g_action[(long)b * A + r.adim + d] = (raw[d] >= -1.0 && raw[d] <= 1.0) ? gav[d] * (d < 3 ? a1.s[d] : a1.sw[d - 3]) / (double)c.S : 0.0;
   }
   if (g_E) g_E[b] = a.w.gpar[b * 4];
   if (g_nu) g_nu[b] = a.w.gpar[b * 4 + 1];
@@ -542,8 +556,9 @@ __global__ void __launch_bounds__(256) plb_adj_pack_gap(PlbArgs a, int slot, con
 }
 // ... and plb_adj_epilogue_rot through the adjoint of plb_kinematics_gap (plb.hip): f = S - 1 ... 0 through the position clamp, the right-multiplied
 // rotation step and max(gap - gap_vel, minimal_gap), whose cotangent passes to gap[f] and -gap_vel where gap[f] - gap_vel > minimal_gap and is zero
-// where it is smaller -- from gpos / grot / ggap to g_prim_pos0, g_prim_rot0, g_prim_gap0 [B,np] and g_action [B,7].
-__global__ void __launch_bounds__(64) plb_adj_epilogue_gap(PlbArgs a, PlbRot r, PlbGap gp, PlbScale sc, const double* action, double* g_prim_pos0, double* g_prim_rot0,
+// where it is smaller -- from gpos / grot / ggap to g_prim_pos0, g_prim_rot0, g_prim_gap0 [B,np] and g_action [B,A], A = 7 + a1.dim (an actuated
+// primitive 1: the base class's sweep with its own block, columns 7 .., and scales).
+__global__ void __launch_bounds__(64) plb_adj_epilogue_gap(PlbArgs a, PlbRot r, PlbGap gp, PlbScale sc, PlbAct1 a1, const double* action, double* g_prim_pos0, double* g_prim_rot0,
                                                            double* g_prim_gap0, double* g_action, double* g_E, double* g_nu, double* g_ys, double* g_fric) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= a.Bcall) return;   // g_action, g_prim_gap0, ... are the caller's [Bcall] arrays
@@ -556,11 +571,17 @@ __global__ void __launch_bounds__(64) plb_adj_epilogue_gap(PlbArgs a, PlbRot r, 
   double* GG = gp.ggap + (long)b * (c.S + 1) * c.np;
   for (int pi = 0; pi < c.np; ++pi) {
     double raw[7] = {0, 0, 0, 0, 0, 0, 0}, av[7] = {0, 0, 0, 0, 0, 0, 0}, gav[7] = {0, 0, 0, 0, 0, 0, 0};
+    const int A = 7 + a1.dim;
     if (pi == 0) {
 #pragma unroll
       for (int d = 0; d < 7; ++d) {
-        raw[d] = action[(long)b * 7 + d];
+        raw[d] = action[(long)b * A + d];
         av[d] = fmin(fmax(raw[d], -1.0), 1.0) * (d < 3 ? sc.s[d] : (d < 6 ? r.sw[d - 3] : gp.sg)) / (double)c.S;
+      }
+    } else if (pi == 1) {
+      for (int d = 0; d < a1.dim; ++d) {
+        raw[d] = action[(long)b * A + 7 + d];
+        av[d] = fmin(fmax(raw[d], -1.0), 1.0) * (d < 3 ? a1.s[d] : a1.sw[d - 3]) / (double)c.S;
       }
     }
     double dq[4], gdq[4] = {0, 0, 0, 0};
@@ -592,7 +613,10 @@ __global__ void __launch_bounds__(64) plb_adj_epilogue_gap(PlbArgs a, PlbRot r, 
     if (g_prim_gap0) g_prim_gap0[(long)b * c.np + pi] = GG[pi];
     if (pi == 0 && g_action)
       for (int d = 0; d < 7; ++d)
-        g_action[(long)b * 7 + d] = (raw[d] >= -1.0 && raw[d] <= 1.0) ? gav[d] * (d < 3 ? sc.s[d] : (d < 6 ? r.sw[d - 3] : gp.sg)) / (double)c.S : 0.0;
+        g_action[(long)b * A + d] = (raw[d] >= -1.0 && raw[d] <= 1.0) ? gav[d] * (d < 3 ? sc.s[d] : (d < 6 ? r.sw[d - 3] : gp.sg)) / (double)c.S : 0.0;
+    if (pi == 1 && g_action)
+      for (int d = 0; d < a1.dim; ++d)
+        g_action[(long)b * A + 7 + d] = (raw[d] >= -1.0 && raw[d] <= 1.0) ? gav[d] * (d < 3 ? a1.s[d] : a1.sw[d - 3]) / (double)c.S : 0.0;
   }
   if (g_E) g_E[b] = a.w.gpar[b * 4];
   if (g_nu) g_nu[b] = a.w.gpar[b * 4 + 1];
@@ -933,11 +957,11 @@ static int plb_step_bwd_impl(const char* who, bool rot, ud_plb* h, int B, const 
   hipLaunchKernelGGL(ud::plb_adj_clear, gc, blk, 0, st, a);
   hipLaunchKernelGGL(ud::plb_adj_reset_counts, dim3((B + 63) / 64), dim3(64), 0, st, a);
   hipLaunchKernelGGL(ud::plb_adj_unpack, gp, blk, 0, st, a, 0, g_x0, g_v0, g_C0, g_F0);
-  if (chop) hipLaunchKernelGGL(ud::plb_adj_epilogue_gap, dim3((B + 63) / 64), dim3(64), 0, st, a, rr, gg, h->ascale, action, g_prim_pos0, g_prim_rot0, g_prim_gap0, g_action,
+  if (chop) hipLaunchKernelGGL(ud::plb_adj_epilogue_gap, dim3((B + 63) / 64), dim3(64), 0, st, a, rr, gg, h->ascale, h->act1, action, g_prim_pos0, g_prim_rot0, g_prim_gap0, g_action,
                                g_E, g_nu, g_yield_stress, g_ground_friction);
-  else if (rot) hipLaunchKernelGGL(ud::plb_adj_epilogue_rot, dim3((B + 63) / 64), dim3(64), 0, st, a, rr, h->ascale, action, g_prim_pos0, g_prim_rot0, g_action, g_E, g_nu,
+  else if (rot) hipLaunchKernelGGL(ud::plb_adj_epilogue_rot, dim3((B + 63) / 64), dim3(64), 0, st, a, rr, h->ascale, h->act1, action, g_prim_pos0, g_prim_rot0, g_action, g_E, g_nu,
                               g_yield_stress, g_ground_friction);
-  else hipLaunchKernelGGL(ud::plb_adj_epilogue, dim3((B + 63) / 64), dim3(64), 0, st, a, h->ascale, action, g_prim_pos0, g_action, g_E, g_nu, g_yield_stress, g_ground_friction);
+  else hipLaunchKernelGGL(ud::plb_adj_epilogue, dim3((B + 63) / 64), dim3(64), 0, st, a, h->ascale, h->act1, action, g_prim_pos0, g_action, g_E, g_nu, g_yield_stress, g_ground_friction);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { ud::set_error("%s: %s", who, hipGetErrorString(e)); return UD_ERR_HIP; }
   return UD_OK;

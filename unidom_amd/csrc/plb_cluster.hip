@@ -75,6 +75,7 @@ struct PclArgs {
   const double *gx, *gv, *gC, *gF, *gpp;   // backward: cotangents of the step outputs (any may be null)
   double *g_action, *g_E, *g_nu, *g_ys, *g_fric;
   PclCk ck;
+  int adim1;                           // primitive 1's action block: 0 (unactuated) or 3; the action row is [3 + adim1], its columns 3 .. 5
   int keep;                            // forward: a checkpoint is written
   double* cg[3];                       // [Bl][G][4] rotating exchange grids: (m, mv) forward, cotangent of v_out backward (rest state: zero)
   unsigned* bar;                       // [Bl][PCL_BAR_STRIDE]: arrival counter, generation word, exit counter (rest state: zero)
@@ -176,12 +177,12 @@ __device__ __forceinline__ int pcl_compact(const int* key, int* klist, unsigned 
 }
 
 // primitive trajectory of the whole step into LDS (forward_kinematics :118-121 + set_velocity :185-192 as plb_pack writes it):
-// P[s + 1] = clamp(P[s] + v), v = clip(action) / S for primitive 0
+// P[s + 1] = clamp(P[s] + v), v = clip(action) / S for primitive 0 and, from its own block, for an actuated primitive 1 (a.adim1 == 3)
 __device__ __forceinline__ void pcl_trajectory(const PclArgs& a, int b, double* s_pos, double* out /* checkpoint rows of this env, or null */) {
   const PlbConst& c = a.c;
   if ((int)threadIdx.x < c.np * 3) {
     const int pi = threadIdx.x / 3, d = threadIdx.x % 3;
-    const double pv = (pi == 0) ? fmin(fmax(a.action[b * 3 + d], -1.0), 1.0) * 1.0 / (double)c.S : 0.0;
+    const double pv = (pi == 0 || a.adim1 != 0) ? fmin(fmax(a.action[(long)b * (3 + a.adim1) + pi * 3 + d], -1.0), 1.0) * 1.0 / (double)c.S : 0.0;
     double cur = a.prim_pos[(long)b * c.np * 3 + pi * 3 + d];
     s_pos[pi * 3 + d] = cur;
     if (out) out[pi * 3 + d] = cur;
@@ -678,8 +679,10 @@ __global__ void __launch_bounds__(PCL_T) pcl_bwd_kernel(const PclArgs a) {
     if (w == 0) {
       if (tid < c.np * 3) {
         const int pi = tid / 3, d = tid % 3;
-        const double raw = (pi == 0) ? a.action[b * 3 + d] : 0.0;
-        const double pv = (pi == 0) ? fmin(fmax(raw, -1.0), 1.0) / (double)S : 0.0;
+        const bool act = pi == 0 || a.adim1 != 0;
+        const long col = (long)b * (3 + a.adim1) + pi * 3 + d;
+        const double raw = act ? a.action[col] : 0.0;
+        const double pv = act ? fmin(fmax(raw, -1.0), 1.0) / (double)S : 0.0;
         double gpv = 0.0;
         // the cotangent of pos[s + 1] is r + Q[s] and that of pos[s] is Q[s - 1] - Q[s] + pass (r + Q[s]): where the clamp passes, Q[s] drops
         // out exactly and r goes on unchanged; where it does not, -Q[s] is all that is left.  Q[-1] = 0: the start position gets r
@@ -692,7 +695,7 @@ __global__ void __launch_bounds__(PCL_T) pcl_bwd_kernel(const PclArgs a) {
           else r = -Q;
         }
         if (a.prim_o) a.prim_o[((long)b * c.np + pi) * 3 + d] = r;
-        if (pi == 0 && a.g_action) a.g_action[b * 3 + d] = (raw >= -1.0 && raw <= 1.0) ? gpv / (double)S : 0.0;
+        if (act && a.g_action) a.g_action[col] = (raw >= -1.0 && raw <= 1.0) ? gpv / (double)S : 0.0;
       }
       if (tid >= 64 && tid < 68) {
         const int k = tid - 64;
@@ -798,7 +801,7 @@ int plb_cluster_reserve(ud_plb* h, int per) {
 
 static ud::PclArgs pcl_args(ud_plb* h, const double* softness, const double* action, const double* E, const double* nu, const double* ys) {
   ud::PclArgs a{};
-  a.c = h->c; a.G = h->G; a.W = h->cl.W;
+  a.c = h->c; a.G = h->G; a.W = h->cl.W; a.adim1 = h->act1.dim;
   a.softness = softness; a.action = action; a.E = E; a.nu = nu; a.ys = ys;
   for (int i = 0; i < 3; ++i) a.cg[i] = h->cl.cg[i];
   a.bar = h->cl.bar; a.gposacc = h->cl.gposacc; a.gpar = h->cl.gpar; a.timeouts = h->cl.timeouts;

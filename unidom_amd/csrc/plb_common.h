@@ -160,6 +160,9 @@ __device__ __forceinline__ void plb_grid_cell(const PlbConst& c, long lin, doubl
 }
 
 struct PlbScale { double s[3]; };   // action scale of primitive 0 (set_velocity: v = clip(action) * scale / substeps)
+// primitive 1's action block (ud_plb_conf.action_dim1): dim 0 = unactuated, 3 = v, 6 = (v, w) of the base class; its columns of the action row
+// [A] sit behind primitive 0's A0, at A0 .. A0 + dim - 1 (Primitives.set_action's running offsets); s, sw: its action.scale[0:3], [3:6]
+struct PlbAct1 { int dim; double s[3], sw[3]; };
 
 // The same for a handle with a general primitive (plb_prim.h): kind 1 collides as Primitive.collide does, kind 0 sticks as above.  A function
 // of its own, and plb_grid_cell left to the letter: the persistent kernels inline that one at the edge of their register budget, and a
@@ -255,6 +258,7 @@ struct ud_plb {
   bool shape = false;       // some primitive is a Box, a Cylinder or a Torus: the GEN = 3 / 4 kernels, which read the kind at run time
   ud::PlbShape shp{};
   ud::PlbScale ascale{{1.0, 1.0, 1.0}};
+  ud::PlbAct1 act1{0, {1.0, 1.0, 1.0}, {1.0, 1.0, 1.0}};   // primitive 1's action block; dim 0: the handle of before
   bool rot_state = false;   // every primitive's orientation is per-env state (the _rot entry points); rot: its arenas and kinematics
   ud::PlbRot rot{};
   bool chop = false;        // primitive 0 is a Chopsticks (the _gap entry points): the GEN = 5 kernels; gap: its arenas and constants

@@ -77,10 +77,17 @@ class PlbConf:
     prim_min_gap = (0.0, 0.0)
     prim_init_gap = (0.0, 0.0)
     action_scale_gap = 1.0
+    # an actuated primitive 1 (ud_plb_conf.action_dim1): 0 = unactuated (the handle of before), 3 = it takes v, 6 = (v, w) of the base class
+    # (needs rot_state).  The action row is [A0 + action_dim1] with primitive 0's A0 columns first (Primitives.set_action's running offsets,
+    # primitives.py:307-311); primitive 1 is scaled by action_scale1 / action_scale_w1 and always follows the base class's kinematics
+    action_dim1 = 0
+    action_scale1 = (1.0, 1.0, 1.0)
+    action_scale_w1 = (1.0, 1.0, 1.0)
     softness = 666.0         # Primitive cfg default, set_softness()
     # True: the handle is created with the unit action scale and `step` applies action.clamp(-1, 1) * action_scale in torch (the kernel's own
     # clip is then the identity; torch's clamp passes the cotangent at equality, as the header specifies) -- a Sphere handle with a scale
-    # thereby runs the persistent kernels (launch_plan() == 2).  Every |action_scale| must be <= 1.  Not with rot_state
+    # thereby runs the persistent kernels (launch_plan() == 2).  Every |action_scale| must be <= 1.  Not with rot_state.
+    # With action_dim1 = 3 primitive 1's block is scaled by action_scale1 likewise
     action_scale_on_host = False
 
 
@@ -114,6 +121,21 @@ class MoveConf(PlbConf):
     prim_friction = (0.0,)
     action_scale = (0.005, 0.005, 0.005)
     action_scale_on_host = True
+
+
+class BimanualConf(MoveConf):
+    """A two-handed task.  THIS PROJECT'S OWN CHOICE: the reference's Primitives slices one action vector over any number of primitives
+    (primitives.py:280-319) but ships no two-handed yml, so there is no file to mirror.  MoveConf's rod with a Sphere of radius 0.025 at each
+    end, each taking three action dimensions (the action row is [B,6]: primitive 0's v, then primitive 1's) with action.scale 0.005.  Both
+    scales are applied on the host, so the handle runs the persistent path."""
+    prim_kind = (0, 0)
+    prim_radius = (0.025, 0.025)
+    prim_h = (0.0, 0.0)
+    prim_init_pos = ((0.745, 0.02, 0.5), (0.255, 0.02, 0.5))
+    prim_rot = ((1.0, 0.0, 0.0, 0.0), (1.0, 0.0, 0.0, 0.0))
+    prim_friction = (0.0, 0.0)
+    action_dim1 = 3
+    action_scale1 = (0.005, 0.005, 0.005)
 
 
 class RopeConf(PlbConf):
@@ -252,7 +274,7 @@ class _PlbStep(torch.autograd.Function):
         g = lambda t: None if t is None else _c(t)
         gx, gv, gC, gF, gpp = map(g, (gx, gv, gC, gF, gpp))
         mk = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
-        ox, ov, oC, oF, op, oa = mk(B, N, 3), mk(B, N, 3), mk(B, N, 3, 3), mk(B, N, 3, 3), mk(B, P, 3), mk(B, 3)
+        ox, ov, oC, oF, op, oa = mk(B, N, 3), mk(B, N, 3), mk(B, N, 3, 3), mk(B, N, 3, 3), mk(B, P, 3), mk(B, sim.action_dim)
         oE, onu, oys, ofr = mk(B), mk(B), mk(B), mk(B)
         stream = _lib.stream(dev)
         ev = sim._prof_begin("bwd")
@@ -336,7 +358,7 @@ class _PlbStepGap(torch.autograd.Function):
         g = lambda t: None if t is None else _c(t)
         gx, gv, gC, gF, gpp, gpr, gpg = map(g, (gx, gv, gC, gF, gpp, gpr, gpg))
         mk = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
-        ox, ov, oC, oF, op, orot, ogap, oa = mk(B, N, 3), mk(B, N, 3), mk(B, N, 3, 3), mk(B, N, 3, 3), mk(B, P, 3), mk(B, P, 4), mk(B, P), mk(B, 7)
+        ox, ov, oC, oF, op, orot, ogap, oa = mk(B, N, 3), mk(B, N, 3), mk(B, N, 3, 3), mk(B, N, 3, 3), mk(B, P, 3), mk(B, P, 4), mk(B, P), mk(B, sim.action_dim)
         oE, onu, oys, ofr = mk(B), mk(B), mk(B), mk(B)
         stream = _lib.stream(dev)
         ev = sim._prof_begin("bwd")
@@ -497,7 +519,17 @@ class PlbSimulator:
         pad = lambda seq, fill: (list(seq)[:P] + [fill] * 2)[:2]
         self.prim_kind = tuple(int(k) for k in pad(cfg.prim_kind, 0))[:P]
         self.rot_state = bool(getattr(cfg, "rot_state", False))
-        self.action_dim = int(getattr(cfg, "action_dim", 3)) or 3
+        # the action row: primitive 0's A0 columns (3, 6, or the Chopsticks' 7), then primitive 1's action_dim1 (Primitives.action_dims)
+        A0 = int(getattr(cfg, "action_dim", 3)) or 3
+        self.action_dim1 = int(getattr(cfg, "action_dim1", 0))
+        self.action_dim = A0 + self.action_dim1
+        self.action_dims = (0, A0, self.action_dim)
+        handle_scale1 = tuple(float(s) for s in getattr(cfg, "action_scale1", (1.0, 1.0, 1.0)))
+        if self._host_scale is not None and self.action_dim1:
+            if any(abs(s) > 1.0 for s in handle_scale1):
+                raise ValueError(f"action_scale_on_host needs every |action_scale1| <= 1: {handle_scale1}")
+            self._host_scale = torch.cat([self._host_scale, torch.tensor(handle_scale1, dtype=torch.float64, device=self.device)])
+            handle_scale1 = (1.0, 1.0, 1.0)
         self.chopsticks = P > 0 and self.prim_kind[0] == 6          # the _gap entry points: PlbState.prim_gap is state
         rot = (C.c_double * 4 * 2)(*[(C.c_double * 4)(*q) for q in pad(cfg.prim_rot, (0.0, 0.0, 0.0, 0.0))])
         shape = (C.c_double * 3 * 2)(*[(C.c_double * 3)(*(list(sc) + [0.0] * 3)[:3]) for sc in pad(getattr(cfg, "prim_shape", ()), (0.0, 0.0, 0.0))])
@@ -511,7 +543,9 @@ class PlbSimulator:
             prim_friction=(C.c_double * 2)(*pad(cfg.prim_friction, 0.0)), action_scale=(C.c_double * 3)(*handle_scale),
             rot_state=int(self.rot_state), action_dim=int(getattr(cfg, "action_dim", 3)),
             action_scale_w=(C.c_double * 3)(*getattr(cfg, "action_scale_w", (1.0, 1.0, 1.0))), prim_shape=shape,
-            min_gap=(C.c_double * 2)(*pad(getattr(cfg, "prim_min_gap", ()), 0.0)), action_scale_gap=float(getattr(cfg, "action_scale_gap", 1.0)))
+            min_gap=(C.c_double * 2)(*pad(getattr(cfg, "prim_min_gap", ()), 0.0)), action_scale_gap=float(getattr(cfg, "action_scale_gap", 1.0)),
+            action_dim1=self.action_dim1, action_scale1=(C.c_double * 3)(*handle_scale1),
+            action_scale_w1=(C.c_double * 3)(*getattr(cfg, "action_scale_w1", (1.0, 1.0, 1.0))))
         self._h = C.c_void_p()
         self.profile = None    # {"fwd": [], "bwd": []}: HIP-event pairs around every step call, on its stream (bench.py)
         self.ground_friction_grad = None   # [B], accumulated by backward() (optimize_ground_friction.grad); reset it by hand
@@ -574,8 +608,8 @@ class PlbSimulator:
         the state tensors / the action / E / nu / yield_stress requires grad, the forward keeps a checkpoint and backward()
         runs the adjoint kernels (substep_grad)."""
         B = state.x.shape[0]
-        if self.chopsticks:     # action [B,7]; orientation and gap are stepped with the position
-            action = torch.as_tensor(action, dtype=torch.float64, device=self.device).reshape(B, 7)
+        if self.chopsticks:     # action [B,7 (+ action_dim1)]; orientation and gap are stepped with the position
+            action = torch.as_tensor(action, dtype=torch.float64, device=self.device).reshape(B, self.action_dim)
             xo, vo, Co, Fo, po, ro, go = _PlbStepGap.apply(self, state.x, state.v, state.C, state.F, state.prim_pos, state.prim_rot, state.prim_gap,
                                                            state.softness, action, state.E, state.nu, state.yield_stress)
             return state._replace(x=xo, v=vo, C=Co, F=Fo, prim_pos=po, prim_rot=ro, prim_gap=go)
@@ -584,7 +618,7 @@ class PlbSimulator:
             xo, vo, Co, Fo, po, ro = _PlbStepRot.apply(self, state.x, state.v, state.C, state.F, state.prim_pos, state.prim_rot, state.softness,
                                                        action, state.E, state.nu, state.yield_stress)
             return state._replace(x=xo, v=vo, C=Co, F=Fo, prim_pos=po, prim_rot=ro)
-        action = torch.as_tensor(action, dtype=torch.float64, device=self.device).reshape(B, 3)
+        action = torch.as_tensor(action, dtype=torch.float64, device=self.device).reshape(B, self.action_dim)
         if self._host_scale is not None:
             action = action.clamp(-1.0, 1.0) * self._host_scale
         xo, vo, Co, Fo, po = _PlbStep.apply(self, state.x, state.v, state.C, state.F, state.prim_pos, state.softness, action,
